@@ -12,7 +12,10 @@ metric value = (|L| + |R|) / step time, whole job.
 
 Usage:
   python bench.py [--gpus N] [--steps K] [--warmup W] [--rows R] [--algorithm hash|sort]
-                  [--how inner|left|right|outer] [--no-verify]
+                  [--how inner|left|right|outer] [--dump-outputs DIR] [--full [--no-verify] [--no-phases]]
+
+A plain run does only what the headline figure needs: set up, warm up, time the
+K steps, write the outputs if --dump-outputs is given, print the JSON line.
 
 With --gpus N > 1 and no torchrun environment, bench.py starts
 `torch.distributed.run --nproc-per-node N` on itself as a child process (one
@@ -20,12 +23,17 @@ rank per GPU, RCCL), the way the reference's run_dist_scaling.py:115-154 starts
 `mpirun -np w`; the parent never touches the GPU.  Under an outer torchrun,
 WORLD_SIZE must equal --gpus (a mismatch exits non-zero).
 
-After the timed region the last timed step's output is checked against an
-independent torch computation of the same join (key-count and payload-sum
-identities, see verify_join; --no-verify skips it), and one extra traced step
-reports per-phase milliseconds (max over ranks; not part of the metric).  At
-N > 1 every rank reports its device, PCI bus id and the process group's world
-size into the JSON line ("ranks"), so the record names the GPUs the ranks ran on.
+With --full, after the timed region the last timed step's output is checked
+against an independent torch computation of the same join (key-count and
+payload-sum identities, see verify_join; --no-verify skips it), and one extra
+traced step reports per-phase milliseconds (max over ranks; not part of the
+metric; --no-phases skips it).  Every rank then reports its device, PCI bus id and
+the process group's world size into the JSON line ("ranks"), so the record names
+the GPUs the ranks ran on.
+
+--dump-outputs DIR writes a fixed sample of the last timed step's output table as
+DIR/<column>.npy (see dump_outputs): the same arguments give the same inputs and
+so the same files, whatever order the join emitted its rows in.
 """
 import argparse
 import json
@@ -35,6 +43,7 @@ import subprocess
 import sys
 import time
 
+import numpy as np
 import torch
 
 REFERENCE_ROWS_PER_S = 4.0e8 / 2.3  # 2 x 200M rows in 2.3 s on 160 CPU cores (provisional row count)
@@ -50,10 +59,16 @@ def parse():
     p.add_argument("--payload-cols", type=int, default=3)
     p.add_argument("--algorithm", default="hash", choices=["hash", "sort"])
     p.add_argument("--key-ratio", type=float, default=0.99)
-    p.add_argument("--no-phases", action="store_true", help="skip the traced per-phase step after the timed region")
+    p.add_argument("--full", action="store_true",
+                   help="also run what the headline figure does not need: the output check against torch, the "
+                        "traced per-phase step and the per-rank device record")
+    p.add_argument("--no-phases", action="store_true", help="with --full: skip the traced per-phase step")
     p.add_argument("--how", default="inner", choices=["inner", "left", "right", "outer"])
-    p.add_argument("--verify", action="store_true", help="(default) check the last output against torch, untimed")
+    p.add_argument("--verify", action="store_true",
+                   help="check the last output against torch, untimed (implied by --full)")
     p.add_argument("--no-verify", action="store_true", help="skip the output check")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write a fixed sample of the last timed step's output columns to DIR/<name>.npy")
     p.add_argument("--sync-steps", action="store_true",
                    help="diagnostic: synchronise the device after every timed step (host never runs ahead)")
     p.add_argument("--force-shuffle", action="store_true",
@@ -219,6 +234,54 @@ def verify_join_against(ctx, out, expect, how="inner") -> dict:
             "rel_err_sum_k": rel[3], "rel_err_sum_l_v0": rel[4], "rel_err_sum_r_v0": rel[5]}
 
 
+DUMP_BUDGET_BYTES = 64 << 20  # all files of one --dump-outputs run together
+DUMP_SEED = 0x5EED
+
+
+def dump_outputs(ctx, out, dirname, rows) -> dict:
+    """Write a fixed sample of the join output `out` as dirname/<column>.npy (float64; int64 keys below
+    2^53 are exact) plus dirname/<column>.valid.npy (float32 0/1) for a column with nulls and
+    dirname/row_count.npy (this rank's whole output row count).  At world > 1 every rank writes its own
+    part of the table as <column>.rank<r>.npy.
+
+    The join does not promise a row order (output slots are claimed with atomics), so the sample is
+    chosen by content, not by position: the rows whose key hashes (seeded multiplicative hash) to one
+    residue of `stride`, sorted by all their columns, first to last.  `stride` depends on the arguments
+    alone (sized so that an output of up to 2 x rows fits the budget); a larger output is cut to the
+    budget after the sort, so the files never exceed DUMP_BUDGET_BYTES in all."""
+    os.makedirs(dirname, exist_ok=True)
+    world, rank = ctx.get_world_size(), ctx.get_rank()
+    suffix = f".rank{rank}" if world > 1 else ""
+    cols = list(out.native.columns())
+    by_name = {c.name: c for c in cols}
+    row_bytes = sum(8 + (4 if c.validity is not None else 0) for c in cols)
+    budget = DUMP_BUDGET_BYTES - 4096 * (2 * len(cols) + 1)  # .npy headers
+    stride = max(1, -(-2 * rows * row_bytes // budget))
+    cap = budget // world // row_bytes
+
+    lk, rk = by_name["l_k"], by_name["r_k"]
+    key = lk.data if lk.validity is None else torch.where(lk.validity.to(torch.bool), lk.data, rk.data)
+    h = (key * -7046029254386353131) >> 33  # 0x9E3779B97F4A7C15 as int64; the product wraps
+    pick = torch.nonzero(torch.remainder(h, stride) == DUMP_SEED % stride).squeeze(1)
+    del key, h
+    arrays = []
+    for c in cols:
+        arrays.append((c.name, c.data.index_select(0, pick).to(torch.float64)))
+        if c.validity is not None:
+            arrays.append((c.name + ".valid", c.validity.index_select(0, pick).to(torch.float32)))
+    order = torch.arange(pick.numel(), device=pick.device)
+    for _, a in reversed(arrays):  # stable sorts, last column first = lexicographic by all columns
+        order = order[torch.sort(a[order], stable=True).indices]
+    order = order[:cap]
+    nbytes = 0
+    for name, a in arrays:
+        arr = a[order].cpu().numpy()
+        np.save(os.path.join(dirname, f"{name}{suffix}.npy"), arr)
+        nbytes += arr.nbytes
+    np.save(os.path.join(dirname, f"row_count{suffix}.npy"), np.array([out.row_count], dtype=np.float64))
+    return {"dir": dirname, "stride": stride, "sample_rows": int(order.numel()), "bytes": nbytes + 8}
+
+
 def rank_record(ctx) -> list:
     """[{rank, device, pci_bus_id, world_size}] of every rank (all-gathered; rank 0 prints it)."""
     import torch.distributed as dist
@@ -290,15 +353,20 @@ def main():
         out_rows = int(rows_t.item())
     elapsed = float(t.item())
 
+    dumped = None
+    if args.dump_outputs and out is not None:
+        dumped = dump_outputs(ctx, out, args.dump_outputs, args.rows)
+
+    # untimed extras, --full only (--verify asks for the output check alone)
     verify = None
-    if not args.no_verify and out is not None:
+    if (args.full or args.verify) and not args.no_verify and out is not None:
         verify = verify_join(ctx, left, right, out, key_range, args.how)
     out = None
-    ranks = rank_record(ctx)
+    ranks = rank_record(ctx) if args.full else None
 
     phases = None
     counters = {}
-    if not args.no_phases:
+    if args.full and not args.no_phases:
         from cylon_amd.utils import trace
         trace.enable_tracing(True)
         trace.reset_tracing()
@@ -347,7 +415,10 @@ def main():
             rec["phases_ms_max_over_ranks"] = phases
         if verify is not None:
             rec["verify"] = verify
-        rec["ranks"] = ranks
+        if ranks is not None:
+            rec["ranks"] = ranks
+        if dumped is not None:
+            rec["dump_outputs"] = dumped
         rec["allocator_timed_region"] = allocator
         if args.sync_steps:
             rec["sync_steps"] = True

@@ -176,7 +176,7 @@ def test_bench_contract_multirank_cpu_rehearsal():
     env = dict(os.environ, CYLON_BENCH_BACKEND="gloo")
     out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                           "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(root, "bench.py"),
-                          "--gpus", "2", "--steps", "2", "--warmup", "1", "--rows", "100000"],
+                          "--gpus", "2", "--steps", "2", "--warmup", "1", "--rows", "100000", "--full"],
                          capture_output=True, text=True, timeout=240, env=env, cwd="/tmp")
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert out.returncode == 0 and len(lines) == 1, out.stderr[-2000:]
@@ -202,7 +202,7 @@ def test_bench_self_launch_four_ranks_cpu():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env["CYLON_BENCH_BACKEND"] = "gloo"
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "4", "--steps", "2",
-                          "--warmup", "1", "--rows", "80000", "--how", "outer"],
+                          "--warmup", "1", "--rows", "80000", "--how", "outer", "--full"],
                          capture_output=True, text=True, timeout=300, env=env, cwd="/tmp")
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert out.returncode == 0 and len(lines) == 1, out.stderr[-2000:]
@@ -215,6 +215,57 @@ def test_bench_self_launch_four_ranks_cpu():
                          capture_output=True, text=True, timeout=120, cwd="/tmp",
                          env=dict(env, WORLD_SIZE="2", RANK="0", LOCAL_RANK="0"))
     assert bad.returncode == 2 and "WORLD_SIZE" in bad.stderr
+
+
+def test_bench_plain_run_is_lean_and_dumps_outputs(tmp_path):
+    """A plain bench.py run (CPU rehearsal) prints the headline fields and none of the --full extras;
+    --dump-outputs writes float .npy files of the last step's output that are identical from run to
+    run, hold exactly the sampled rows of the join (checked against pandas) and stay under 64 MB."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    env["CYLON_BENCH_BACKEND"] = "gloo"
+    rows = 600_000  # large enough that the dump is a sample (every second key), small enough for a CPU join
+    dumps = []
+    for d in ("a", "b"):
+        out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2",
+                              "--warmup", "1", "--rows", str(rows), "--dump-outputs", str(tmp_path / d)],
+                             capture_output=True, text=True, timeout=240, env=env, cwd=str(tmp_path))
+        lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+        assert out.returncode == 0 and len(lines) == 1, out.stderr[-2000:]
+        rec = json.loads(lines[0])
+        for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert k in rec
+        assert rec["steps"] == 2 and rec["ms_per_step"] > 0
+        assert rec["value"] == pytest.approx(2 * rows / (rec["ms_per_step"] / 1000.0))
+        for k in ("verify", "phases_ms_max_over_ranks", "ranks"):
+            assert k not in rec
+        files = sorted(os.listdir(tmp_path / d))
+        assert files == sorted(f"{s}_{c}.npy" for s in "lr" for c in ("k", "v0", "v1", "v2")) + ["row_count.npy"]
+        dumps.append({f[:-4]: np.load(tmp_path / d / f) for f in files})
+        assert sum(os.path.getsize(tmp_path / d / f) for f in files) <= 64 << 20
+    a, b = dumps
+    assert all(v.dtype in (np.float32, np.float64) for v in a.values())
+    assert all(np.array_equal(a[k], b[k]) for k in a)
+    assert int(a["row_count"][0]) == rec["config"]["output_rows"] and 100 < len(a["l_k"]) < a["row_count"][0]
+    assert np.array_equal(a["l_k"], a["r_k"])
+    # the sample is every output row of its keys: the same rows as a pandas join restricted to them
+    import torch
+    rels = []
+    for seed in (1000, 2000):
+        g = torch.Generator().manual_seed(seed)
+        k = torch.randint(0, int(0.99 * rows), (rows,), generator=g, dtype=torch.int64)
+        rels.append(pd.DataFrame({"k": k.numpy(), **{f"v{c}": torch.rand(rows, generator=g, dtype=torch.float64).numpy()
+                                                     for c in range(3)}}))
+    keys = np.unique(a["l_k"]).astype(np.int64)
+    exp = rels[0][rels[0].k.isin(keys)].merge(rels[1][rels[1].k.isin(keys)], on="k", suffixes=("_l", "_r"))
+    exp = exp.sort_values(list(exp.columns)).to_numpy()
+    got = np.stack([a[n] for n in ("l_k", "l_v0", "l_v1", "l_v2", "r_v0", "r_v1", "r_v2")], axis=1)
+    got = got[np.lexsort(got.T[::-1])]
+    assert np.array_equal(got, exp)
 
 
 def _op_graph_uneven(ctx):

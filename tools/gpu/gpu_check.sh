@@ -1,11 +1,13 @@
 set -o pipefail
-cd $GRAFT_REPO_ROOT
+ROOT=$(cd "$(dirname "$0")/../.." && pwd)
+OUT=${OUT:-$ROOT/bench_out}
+cd $ROOT
 export TMPDIR=/tmp
-mkdir -p gpurun_out
-timeout -k 10 600 python -m pytest tests/test_gpu_kernels.py -x -q > gpurun_out/pytest_gpu.log 2>&1
-echo "pytest exit $?" >> gpurun_out/pytest_gpu.log
-timeout -k 10 300 python __graft_entry__.py smoke > gpurun_out/smoke.log 2>&1 && \
-timeout -k 10 300 python bench.py --rows 100000000 --steps 3 --warmup 1 > gpurun_out/bench_100m.log 2>&1 && \
-timeout -k 10 600 python bench.py --steps 3 --warmup 1 > gpurun_out/bench_1b.log 2>&1
+mkdir -p $OUT
+timeout -k 10 600 python -m pytest tests/test_gpu_kernels.py -x -q > $OUT/pytest_gpu.log 2>&1
+echo "pytest exit $?" >> $OUT/pytest_gpu.log
+timeout -k 10 300 python __graft_entry__.py smoke > $OUT/smoke.log 2>&1 && \
+timeout -k 10 300 python bench.py --full --rows 100000000 --steps 3 --warmup 1 > $OUT/bench_100m.log 2>&1 && \
+timeout -k 10 600 python bench.py --full --steps 3 --warmup 1 > $OUT/bench_1b.log 2>&1
 echo "chain exit $?"
-tail -3 gpurun_out/pytest_gpu.log; cat gpurun_out/smoke.log gpurun_out/bench_100m.log gpurun_out/bench_1b.log | tail -20
+tail -3 $OUT/pytest_gpu.log; cat $OUT/smoke.log $OUT/bench_100m.log $OUT/bench_1b.log | tail -20

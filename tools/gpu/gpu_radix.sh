@@ -1,12 +1,14 @@
 # Radix-join iteration: correctness tests, 1B bench, kernel profile.
 set -o pipefail
-cd $GRAFT_REPO_ROOT
+ROOT=$(cd "$(dirname "$0")/../.." && pwd)
+OUT=${OUT:-$ROOT/bench_out}
+cd $ROOT
 export TMPDIR=/tmp
-mkdir -p gpurun_out
-timeout -k 10 300 python -m pytest tests/test_gpu_kernels.py -m gpu -q -k "radix or large_join" > gpurun_out/pytest_radix.log 2>&1
-rc=$?; echo "radix pytest exit $rc" >> gpurun_out/pytest_radix.log; tail -15 gpurun_out/pytest_radix.log
+mkdir -p $OUT
+timeout -k 10 300 python -m pytest tests/test_gpu_kernels.py -m gpu -q -k "radix or large_join" > $OUT/pytest_radix.log 2>&1
+rc=$?; echo "radix pytest exit $rc" >> $OUT/pytest_radix.log; tail -15 $OUT/pytest_radix.log
 [ $rc -eq 0 ] || exit $rc
-timeout -k 10 600 python bench.py --steps 3 --warmup 1 > gpurun_out/bench_1b.log 2>&1 || exit 1
-grep '^{' gpurun_out/bench_1b.log
-cd /tmp && timeout -k 10 600 rocprofv3 --kernel-trace --stats -d $GRAFT_REPO_ROOT/gpurun_out/prof_join1b -o join -- python3 $GRAFT_REPO_ROOT/bench.py --steps 1 --warmup 1 > $GRAFT_REPO_ROOT/gpurun_out/prof_join1b.log 2>&1 || exit 1
-cd $GRAFT_REPO_ROOT && python tools/prof_summary.py gpurun_out/prof_join1b/join_results.db 30 > gpurun_out/prof_join1b_summary.txt; cat gpurun_out/prof_join1b_summary.txt
+timeout -k 10 600 python bench.py --full --steps 3 --warmup 1 > $OUT/bench_1b.log 2>&1 || exit 1
+grep '^{' $OUT/bench_1b.log
+cd /tmp && timeout -k 10 600 rocprofv3 --kernel-trace --stats -d $OUT/prof_join1b -o join -- python3 $ROOT/bench.py --steps 1 --warmup 1 > $OUT/prof_join1b.log 2>&1 || exit 1
+cd $ROOT && python tools/prof_summary.py $OUT/prof_join1b/join_results.db 30 > $OUT/prof_join1b_summary.txt; cat $OUT/prof_join1b_summary.txt
