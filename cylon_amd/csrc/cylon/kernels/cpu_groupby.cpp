@@ -195,11 +195,15 @@ void group_quantile(const ColView &v, const int64_t *perm, const int64_t *offs, 
       valid[g] = 0;
       continue;
     }
-    const double np = (double)cnt * q, j = std::floor(np), gg = np - j;
+    const double np = (double)cnt * q, j = std::floor(np);
+    bool whole = np == j;
     int64_t pos = (int64_t)j;
-    if (pos >= cnt) pos = cnt - 1;
-    out[g] = (gg == 0.0 && pos > 0) ? 0.5 * (as_double(v, perm[b + pos - 1]) + as_double(v, perm[b + pos]))
-                                    : as_double(v, perm[b + pos]);
+    if (pos >= cnt) {  // q = 1: the maximum itself, no average with the value below it
+      pos = cnt - 1;
+      whole = false;
+    }
+    out[g] = (whole && pos > 0) ? 0.5 * (as_double(v, perm[b + pos - 1]) + as_double(v, perm[b + pos]))
+                                : as_double(v, perm[b + pos]);
     valid[g] = 1;
   }
 }

@@ -304,8 +304,9 @@ __global__ void k_rg_pack(const int64_t *__restrict__ offs, const int64_t *__res
 //      (q_wave_select), a mixed bucket is sorted by (key, value) in registers (q_wave_bitonic);
 //      rows of larger buckets count their rank over the bucket;
 //   3. the type-2 position (global path k_quantile: np = nv q, j = floor(np), pos = min(j, nv - 1),
-//      the mean with the (pos - 1)-th when np is whole) is written per group at a slot from an LDS
-//      counter (gcount per partition; radix_groupby_pack packs the slabs).
+//      the mean with the (pos - 1)-th when np is whole and j < nv -- q = 1 is the maximum) is
+//      written per group at a slot from an LDS counter (gcount per partition; radix_groupby_pack
+//      packs the slabs).
 // Nulls rank after every value (excluded, as the global path does).  Values compare as
 // order-preserving images of their doubles (NaN canonicalised).
 constexpr int kQCap = 4096, kQThreads = 512, kQPer = kQCap / kQThreads, kQBBits = 11, kQBuckets = 1 << kQBBits;
@@ -562,9 +563,12 @@ __device__ __forceinline__ void q_rank_bucket(QKV *skv, int e0, int sz, double q
     mn = q_uniform64(mn);
     mx = q_uniform64(mx);
     const double np = (double)nv * q, jf = floor(np);
-    const bool whole = np == jf;
+    bool whole = np == jf;
     int pos = (int)jf;
-    if (pos >= (int)nv) pos = (int)nv - 1;
+    if (pos >= (int)nv) {  // q = 1: the maximum itself, no average with the value below it
+      pos = (int)nv - 1;
+      whole = false;
+    }
     pos = __builtin_amdgcn_readfirstlane(pos);
     uint64_t at = mn, below = mn;
     if (mn != mx) {
@@ -676,9 +680,12 @@ __device__ __forceinline__ void q_rank_bucket(QKV *skv, int e0, int sz, double q
     if (!last_valid[s]) continue;
     const int nv = e - start[s] + 1;
     const double np = (double)nv * q, jf = floor(np);
-    const bool whole = np == jf;
+    bool whole = np == jf;
     int pos = (int)jf;
-    if (pos >= nv) pos = nv - 1;
+    if (pos >= nv) {  // q = 1: the maximum itself
+      pos = nv - 1;
+      whole = false;
+    }
     const double at = q_unimage(skv[e0 + start[s] + pos].v);
     const double qv = (whole && pos > 0) ? 0.5 * (q_unimage(skv[e0 + start[s] + pos - 1].v) + at) : at;
     double mn = 0.0;
@@ -895,9 +902,12 @@ __global__ __launch_bounds__(kQThreads) __attribute__((amdgpu_waves_per_eu(4))) 
       }
       if (v == ~0ull) continue;
       const double np = (double)nv * q, jf = floor(np);
-      const bool whole = np == jf;  // (a comparison: `np - j == 0` is contracted into an fma)
+      bool whole = np == jf;  // (a comparison: `np - j == 0` is contracted into an fma)
       int pos = (int)jf;
-      if (pos >= nv) pos = nv - 1;
+      if (pos >= nv) {  // q = 1: the maximum itself
+        pos = nv - 1;
+        whole = false;
+      }
       if (rank != pos) continue;
       const double qv = (whole && pos > 0) ? 0.5 * (q_unimage(below) + q_unimage(v)) : q_unimage(v);
       q_emit<FUSE>(&s_nout, okeys, oq, ovalid, fz, n, b, k, true, qv, gsum, nv, q_unimage(gmin), q_unimage(gmax));

@@ -915,9 +915,21 @@ static TablePtr radix_groupby_composed(const TablePtr &t, const std::vector<int>
   return Table::Make(t->GetContext(), std::move(out));
 }
 
+// q of a QUANTILE must lie in [0, 1]: a negative or NaN q would index outside the group's rows
+// (the comparison form also refuses NaN).  Checked at the entries, before any dispatch.
+static void check_quantile(double q) {
+  CYLON_CHECK(q >= 0.0 && q <= 1.0, Code::Invalid, "quantile q must be in [0, 1], got " << q);
+}
+
+static void check_aggs(const std::vector<AggSpec> &aggs) {
+  for (const auto &a : aggs)
+    if (a.op == AGG_QUANTILE) check_quantile(a.quantile);
+}
+
 static TablePtr groupby_with(const TablePtr &t, const std::vector<int> &keys, const std::vector<AggSpec> &aggs,
                              bool presorted) {
   CYLON_CHECK(!keys.empty(), Code::Invalid, "group-by needs at least one key column");
+  check_aggs(aggs);
   if (!presorted) {
     if (TablePtr r = radix_groupby(t, keys, aggs)) return r;
     if (TablePtr r = radix_groupby_composed(t, keys, aggs)) return r;
@@ -953,6 +965,7 @@ static bool decomposable(int op) {
 
 TablePtr DistributedHashGroupBy(const TablePtr &t, const std::vector<int> &keys, const std::vector<AggSpec> &aggs) {
   auto ctx = t->GetContext();
+  check_aggs(aggs);  // (before the shuffle)
   if (!ctx->ShuffleRequired()) return HashGroupBy(t, keys, aggs);
   bool all_dec = true;
   for (const auto &a : aggs) all_dec &= decomposable(a.op);
@@ -1098,6 +1111,7 @@ TablePtr DistributedHashGroupBy(const TablePtr &t, const std::vector<int> &keys,
 TablePtr DistributedPipelineGroupBy(const TablePtr &t, const std::vector<int> &keys,
                                     const std::vector<AggSpec> &aggs) {
   auto ctx = t->GetContext();
+  check_aggs(aggs);  // (before the shuffle)
   std::vector<int> cols = keys;
   std::vector<AggSpec> remapped;
   for (const auto &a : aggs) {
@@ -1118,6 +1132,7 @@ TablePtr DistributedPipelineGroupBy(const TablePtr &t, const std::vector<int> &k
 // scalar aggregates (K12 + allreduce)
 // ---------------------------------------------------------------------------
 TablePtr Aggregate(const TablePtr &t, int col, int op, double quantile, int ddof, bool distributed) {
+  if (op == AGG_QUANTILE) check_quantile(quantile);
   auto ctx = t->GetContext();
   const bool dist = distributed && ctx->GetWorldSize() > 1;
   auto comm = ctx->GetCommunicator();
