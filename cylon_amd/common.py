@@ -56,6 +56,8 @@ class JoinType(IntEnum):
     LEFT = 1
     RIGHT = 2
     FULL_OUTER = 3
+    LEFT_SEMI = 4  # 4 and 5 are additions to the reference numbering: left's columns only
+    LEFT_ANTI = 5
 
 
 class JoinAlgorithm(IntEnum):
@@ -64,9 +66,12 @@ class JoinAlgorithm(IntEnum):
 
 
 _JT = {"inner": JoinType.INNER, "left": JoinType.LEFT, "right": JoinType.RIGHT, "outer": JoinType.FULL_OUTER,
-       "full_outer": JoinType.FULL_OUTER, "fullouter": JoinType.FULL_OUTER}
+       "full_outer": JoinType.FULL_OUTER, "fullouter": JoinType.FULL_OUTER,
+       "semi": JoinType.LEFT_SEMI, "left_semi": JoinType.LEFT_SEMI, "leftsemi": JoinType.LEFT_SEMI,
+       "anti": JoinType.LEFT_ANTI, "left_anti": JoinType.LEFT_ANTI, "leftanti": JoinType.LEFT_ANTI}
 _JA = {"sort": JoinAlgorithm.SORT, "hash": JoinAlgorithm.HASH}
-_JT_STR = {JoinType.INNER: "inner", JoinType.LEFT: "left", JoinType.RIGHT: "right", JoinType.FULL_OUTER: "outer"}
+_JT_STR = {JoinType.INNER: "inner", JoinType.LEFT: "left", JoinType.RIGHT: "right", JoinType.FULL_OUTER: "outer",
+           JoinType.LEFT_SEMI: "semi", JoinType.LEFT_ANTI: "anti"}
 
 
 class JoinConfig:

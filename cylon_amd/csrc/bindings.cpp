@@ -42,14 +42,20 @@ class PySendCb : public net::ChannelSendCallback {
 };
 
 at::Device parse_device(const std::string &s) { return at::Device(s); }
+}  // namespace
 
+// also used by bindings_ops.cpp
 join::config::JoinType parse_join_type(const std::string &t) {
   if (t == "inner") return join::config::INNER;
   if (t == "left") return join::config::LEFT;
   if (t == "right") return join::config::RIGHT;
   if (t == "outer" || t == "full_outer" || t == "fullouter") return join::config::FULL_OUTER;
+  if (t == "semi" || t == "left_semi" || t == "leftsemi") return join::config::LEFT_SEMI;
+  if (t == "anti" || t == "left_anti" || t == "leftanti") return join::config::LEFT_ANTI;
   CYLON_THROW(Code::Invalid, "unsupported join type '" << t << "'");
 }
+
+namespace {
 
 join::config::JoinAlgorithm parse_join_algo(const std::string &a) {
   if (a == "hash") return join::config::HASH;

@@ -22,6 +22,17 @@
 namespace py = pybind11;
 using namespace cylon;
 
+join::config::JoinType parse_join_type(const std::string &t);  // bindings.cpp
+
+// join type of the operator / registry bindings: the semi / anti spellings through parse_join_type,
+// every other string as these bindings always read it
+static join::config::JoinType op_join_type(const std::string &type) {
+  using namespace join::config;
+  for (const char *s : {"semi", "left_semi", "leftsemi", "anti", "left_anti", "leftanti"})
+    if (type == s) return parse_join_type(type);
+  return type == "left" ? LEFT : type == "right" ? RIGHT : type == "outer" ? FULL_OUTER : INNER;
+}
+
 static std::vector<ops::AggSpec> make_specs(const std::vector<int> &cols, const std::vector<int> &op_ids,
                                             const std::vector<double> &qs, const std::vector<int> &ddofs) {
   CYLON_CHECK(cols.size() == op_ids.size(), Code::Invalid, "aggregate columns and ops differ in length");
@@ -287,7 +298,7 @@ void register_extended_ops(py::module &m) {
          const std::string &type, const std::string &algo, const std::vector<int> &lc, const std::vector<int> &rc,
          const std::string &lp, const std::string &rp, int num_splits) {
         using namespace join::config;
-        const JoinType jt = type == "left" ? LEFT : type == "right" ? RIGHT : type == "outer" ? FULL_OUTER : INNER;
+        const JoinType jt = op_join_type(type);
         const JoinAlgorithm ja = algo == "hash" ? HASH : SORT;
         graph::DisJoinOpConfig cfg{num_splits, JoinConfig(jt, lc, rc, ja, lp, rp)};
         std::vector<TablePtr> out;
@@ -321,7 +332,7 @@ void register_extended_ops(py::module &m) {
       [](const std::string &l, const std::string &r, const std::string &type, const std::string &algo,
          const std::vector<int> &lc, const std::vector<int> &rc, const std::string &dest, bool distributed) {
         using namespace join::config;
-        const JoinType jt = type == "left" ? LEFT : type == "right" ? RIGHT : type == "outer" ? FULL_OUTER : INNER;
+        const JoinType jt = op_join_type(type);
         JoinConfig cfg(jt, lc, rc, algo == "hash" ? HASH : SORT);
         Status s = distributed ? DistributedJoinTables(l, r, cfg, dest) : JoinTables(l, r, cfg, dest);
         return std::make_pair(s.get_code(), s.get_msg());  // converted after the GIL is re-acquired

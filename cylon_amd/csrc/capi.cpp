@@ -44,7 +44,7 @@ int status(const Status &s) { return s.is_ok() ? 0 : fail(s.get_code(), s.get_ms
 join::config::JoinConfig make_cfg(int jt, int alg, int l, int r) {
   using namespace join::config;
   const JoinType t = jt == 1 ? JoinType::LEFT : jt == 2 ? JoinType::RIGHT : jt == 3 ? JoinType::FULL_OUTER
-                                                                                     : JoinType::INNER;
+                     : jt == 4 ? JoinType::LEFT_SEMI : jt == 5 ? JoinType::LEFT_ANTI : JoinType::INNER;
   const JoinAlgorithm a = alg == 1 ? JoinAlgorithm::HASH : JoinAlgorithm::SORT;
   return JoinConfig(t, l, r, a);
 }

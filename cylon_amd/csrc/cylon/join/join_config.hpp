@@ -13,7 +13,9 @@ namespace cylon {
 namespace join {
 namespace config {
 
-enum JoinType { INNER = 0, LEFT = 1, RIGHT = 2, FULL_OUTER = 3 };
+// 0-3 are the reference's numbering; LEFT_SEMI / LEFT_ANTI (existence joins: left's columns only,
+// docs/semantics.md) are additions
+enum JoinType { INNER = 0, LEFT = 1, RIGHT = 2, FULL_OUTER = 3, LEFT_SEMI = 4, LEFT_ANTI = 5 };
 enum JoinAlgorithm { SORT = 0, HASH = 1 };
 
 class JoinConfig {
@@ -49,6 +51,8 @@ class JoinConfig {
   CYLON_JOIN_FACTORY(LeftJoin, LEFT)
   CYLON_JOIN_FACTORY(RightJoin, RIGHT)
   CYLON_JOIN_FACTORY(FullOuterJoin, FULL_OUTER)
+  CYLON_JOIN_FACTORY(LeftSemiJoin, LEFT_SEMI)
+  CYLON_JOIN_FACTORY(LeftAntiJoin, LEFT_ANTI)
 #undef CYLON_JOIN_FACTORY
 
   JoinType GetType() const { return type_; }

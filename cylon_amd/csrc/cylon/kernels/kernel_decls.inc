@@ -392,6 +392,21 @@ int64_t setop_rows_per_part();
 void setop_dedup(const uint64_t *ph, const int64_t *prow, const int64_t *offs, int64_t nparts, int64_t nl, int op,
                  bool keep_last, const ColView *lcols, const ColView *rcols, int ncols, uint8_t *mask, int64_t *exc,
                  int *bad, void *stream);
+/* Left semi / anti join mark (semi_join.hip; CPU twin cpu_semi.cpp).  rkeys: right int64 key images,
+   partition p = [roffs[p], roffs[p + 1]); lkeys / lrow: left (key, row id) pairs partitioned the same
+   way by loffs (lrow == nullptr: row id = position, nparts == 1).  mask: one byte per left row,
+   initialised by the caller to 0 (semi) or 1 (anti); only MATCHING rows are written (1 / 0).
+   *matched = matching left rows; *overflow = 1 when a partition's distinct right keys exceed
+   semi_join_capacity() (mask undefined; the CPU twin never overflows).
+   GPU only: work items (ipart[i], islice[i]) = slice islice[i] (semi_join_slice_rows() rows) of left
+   partition ipart[i] (both nullptr with nparts == 1: item i = slice i); dkeys / dmeta = workspace of
+   as many int64 as rkeys and of nparts int64. */
+int64_t semi_join_capacity();
+int64_t semi_join_slice_rows();
+void semi_join_mark(const int64_t *rkeys, const int64_t *roffs, const int64_t *lkeys, const int64_t *lrow,
+                    const int64_t *loffs, int64_t nparts, int anti, uint8_t *mask, int64_t *matched, int *overflow,
+                    const int64_t *ipart, const int64_t *islice, int64_t nitems, int64_t *dkeys, int64_t *dmeta,
+                    void *stream);
 /* shuffle wire format: int64 values shipped as uint32 offsets from a global base (range < 2^32) */
 void narrow_i64(const int64_t *in, int64_t n, int64_t base, uint32_t *out, void *stream);
 void widen_u32(const uint32_t *in, int64_t n, int64_t base, int64_t *out, void *stream);

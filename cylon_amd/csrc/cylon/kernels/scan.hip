@@ -336,6 +336,7 @@ void preload_range();
 void preload_range_join();
 void preload_seg_sort();
 void preload_select();
+void preload_semi_join();
 void preload_sort();
 void preload_strcast();
 
@@ -360,6 +361,7 @@ void preload_device_code() {
   preload_scan();
   preload_seg_sort();
   preload_select();
+  preload_semi_join();
   preload_sort();
   preload_strcast();
 }

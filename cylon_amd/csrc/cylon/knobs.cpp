@@ -17,7 +17,7 @@ const std::vector<KnobInfo> &Registry() {
       {"H2D_CHUNK_MB", "runtime", "pinned staged host-to-device ingest: chunk size"},
       {"H2D_THREADS", "runtime", "pinned staged host-to-device ingest: copy threads"},
       // path thresholds (tests force the fast paths on small tables)
-      {"RADIX_JOIN_MIN_ROWS", "threshold", "smallest side from which joins take the LDS radix path"},
+      {"RADIX_JOIN_MIN_ROWS", "threshold", "smallest side from which joins take the LDS radix path (semi / anti joins: left rows, default 2^20; their right side may be any size)"},
       {"RADIX_GROUPBY_MIN_ROWS", "threshold", "rows from which group-bys take the LDS radix path"},
       {"RADIX_SETOP_MIN_ROWS", "threshold", "rows from which union / intersect / subtract / unique take the radix path"},
       {"RADIX_SORT_MIN_ROWS", "threshold", "rows from which sorts take the row-moving radix passes"},
@@ -36,7 +36,7 @@ const std::vector<KnobInfo> &Registry() {
       {"RJ_ESTIMATE_SCALE", "test", "scales the sampled output estimate (< 1 forces the exact rerun)"},
       {"RJ_SHARE_KEY", "test", "0: an inner join writes the build side's key column instead of sharing the probe side's"},
       {"RJ_VAR_WORDS", "test", "0: variable-length string keys / payloads travel as a row number + byte gather, not padded words"},
-      {"RJ_EXTRA_BITS", "test", "extra join partition bits (finer partitions)"},
+      {"RJ_EXTRA_BITS", "test", "extra join partition bits (finer partitions; semi / anti joins too)"},
       {"RJ_SPLIT_ROWS", "test", "build rows per chunk of a split (skewed) join partition (default: LDS capacity)"},
       {"SORT_LOOKBACK", "test", "0: sorts use the exact per-tile histogram passes"},
       {"PARTITION_LOOKBACK", "test", "0: stable two-pass hash partitions use exact tile histograms"},

@@ -24,6 +24,7 @@
 #include <cstdlib>
 #include <limits>
 
+#include "relational.hpp"
 #include "util.hpp"
 #include "../trace.hpp"
 
@@ -1007,12 +1008,16 @@ static TablePtr radix_join(const Exec &ex, const TablePtr &left, const TablePtr 
 static std::pair<at::Tensor, at::Tensor> join_impl(TablePtr left, TablePtr right, const JoinConfig &cfg,
                                                    bool allow_reorder, TablePtr *lout, TablePtr *rout);
 
+static bool is_semi(JoinType jt) { return jt == JoinType::LEFT_SEMI || jt == JoinType::LEFT_ANTI; }
+static std::pair<at::Tensor, at::Tensor> semi_join_indices(const TablePtr &left, const TablePtr &right,
+                                                           const JoinConfig &cfg);
+
 std::pair<at::Tensor, at::Tensor> JoinIndices(const TablePtr &left, const TablePtr &right, const JoinConfig &cfg) {
+  if (is_semi(cfg.GetType())) return semi_join_indices(left, right, cfg);
   return join_impl(left, right, cfg, false, nullptr, nullptr);
 }
 
-static std::pair<at::Tensor, at::Tensor> join_impl(TablePtr left, TablePtr right, const JoinConfig &cfg,
-                                                   bool allow_reorder, TablePtr *lout, TablePtr *rout) {
+static void check_join_keys(const TablePtr &left, const TablePtr &right, const JoinConfig &cfg) {
   const auto &lc = cfg.GetLeftColumnIdx();
   const auto &rc = cfg.GetRightColumnIdx();
   CYLON_CHECK(lc.size() == rc.size(), Code::Invalid, "left/right key counts differ");
@@ -1026,6 +1031,13 @@ static std::pair<at::Tensor, at::Tensor> join_impl(TablePtr left, TablePtr right
     CYLON_CHECK(a == b || both_int, Code::TypeError,
                 "join key types differ: " << a.ToString() << " vs " << b.ToString());
   }
+}
+
+static std::pair<at::Tensor, at::Tensor> join_impl(TablePtr left, TablePtr right, const JoinConfig &cfg,
+                                                   bool allow_reorder, TablePtr *lout, TablePtr *rout) {
+  const auto &lc = cfg.GetLeftColumnIdx();
+  const auto &rc = cfg.GetRightColumnIdx();
+  check_join_keys(left, right, cfg);
   Exec ex(left->device());
   const bool exact = lc.size() == 1 && simple_key(left->column(lc[0])) && simple_key(right->column(rc[0])) &&
                      left->column(lc[0]).type == right->column(rc[0]).type;
@@ -2158,9 +2170,165 @@ static TablePtr radix_join_any(const Exec &ex, const TablePtr &left, const Table
   return FilterByMask(res, bad.logical_not());
 }
 
+// ---------------------------------------------------------------------------
+// Left semi / anti join (docs/semantics.md "Semi / anti join"): the left rows whose key occurs /
+// does not occur on the right, in left's order, left's columns only.
+//
+// Radix path (device, left >= 2^20 rows or RADIX_JOIN_MIN_ROWS, exact int64 key image from radix_keys):
+// kernels/semi_join.hip marks a byte mask indexed by left row id from an LDS set of each
+// partition's distinct right keys.  Only 8 B/row of the right side and 16 B/row of the left side
+// move, never a payload column, so var-width payload stays on this path; a small right side is
+// one partition and nothing moves at all.
+// General path (CPU contexts without a single simple key, small inputs, string / binary / hashed
+// keys, LDS overflow): inner pairs of left against the DISTINCT right keys (at most one per left
+// row), marked into the mask.
+// ---------------------------------------------------------------------------
+// left rows from which the radix path runs (the right side may be any size: a small one is the
+// best case).  The joins' threshold knob, with a lower default: only 16 B/row move here.
+static int64_t semi_join_min_rows() { return knobs::Int("RADIX_JOIN_MIN_ROWS", int64_t(1) << 20); }
+
+struct SemiRows {
+  at::Tensor mask;      // one byte per left row
+  bool invert = false;  // the surviving rows are the mask's zero bytes
+  int64_t kept = -1;    // surviving rows where known without a compaction
+};
+
+// mask from exact key images; false: not usable (LDS overflow, ranking guard), take the general path
+static bool semi_mark_exact(const Exec &ex, at::Tensor lk, at::Tensor rk, bool anti, SemiRows *out) {
+  const int64_t nl = lk.numel(), nr = rk.numel();
+  at::Tensor mask = anti ? at::ones({nl}, ex.opts(at::kByte)) : ex.zeros_u8(nl);
+  at::Tensor matched = ex.empty_i64(1);
+  at::Tensor over = at::empty({1}, ex.opts(at::kInt));
+  auto whole = [&](int64_t n) { return at::tensor(std::vector<int64_t>{0, n}, at::kLong).to(ex.device); };
+  if (!ex.gpu) {
+    at::Tensor roffs = whole(nr), loffs = whole(nl);
+    cpu::semi_join_mark(ptr<int64_t>(rk), ptr<int64_t>(roffs), ptr<int64_t>(lk), nullptr, ptr<int64_t>(loffs), 1,
+                        anti, ptr<uint8_t>(mask), ptr<int64_t>(matched), over.data_ptr<int>(), nullptr, nullptr, 0,
+                        nullptr, nullptr, nullptr);
+  } else {
+    CYLON_PHASE("join.semi.radix", ex.device);
+    trace::add_counter("join.semi.radix", 1);
+    // the join's rule (radix_join `fits`), with the right rows as the upper bound of a partition's
+    // distinct keys: the mean partition sits 8 Poisson sigma (+16 rows) below the LDS set's capacity
+    const int64_t cap = hip::semi_join_capacity(), S = hip::semi_join_slice_rows();
+    auto fits = [&](int64_t mean) { return (double)mean + 8.0 * std::sqrt((double)mean) + 16.0 <= (double)cap; };
+    int bits = 0;
+    while (bits < 24 && !fits((nr + (int64_t(1) << bits) - 1) >> bits)) ++bits;
+    if (const int64_t xb = knobs::Int("RJ_EXTRA_BITS", 0))  // test knob: finer partitions
+      bits = std::min(bits + (int)std::max<int64_t>(0, xb), 2 * 10);
+    const int64_t nparts = int64_t(1) << bits;
+    trace::add_counter("join.semi.parts", nparts);
+    at::Tensor roffs, loffs, lrow, ipart, islice;
+    int64_t nitems = (nl + S - 1) / S;
+    if (bits == 0) {  // broadcast case: no partition pass, the kernel reads the keys in place
+      roffs = whole(nr);
+      loffs = whole(nl);
+    } else {
+      rk = RadixPartition(ex, {rk}, {8}, bits, &roffs, nullptr, nullptr, /*stable=*/false)[0];
+      // left (key, row id) pairs; the row ids are generated by the first pass
+      std::vector<at::Tensor> lp = RadixPartition(ex, {lk, at::Tensor()}, {8, 8}, bits, &loffs);
+      lk = lp[0];
+      lrow = lp[1];
+      if (hip::rp_take_order_violation(ex.stream)) {  // ranking guard of a stable pass fired
+        trace::add_counter("join.semi.order_violation_fallback", 1);
+        return false;
+      }
+      // work items: (partition, slice of S of its left rows), partition-major
+      at::Tensor cnt = at::div(loffs.slice(0, 1, nparts + 1) - loffs.slice(0, 0, nparts) + (S - 1), S, "floor");
+      ipart = at::repeat_interleave(cnt);
+      nitems = ipart.numel();
+      islice = at::arange(nitems, ex.opts(at::kLong)) - (at::cumsum(cnt, 0) - cnt).index_select(0, ipart);
+    }
+    at::Tensor dkeys = ex.empty_i64(nr), dmeta = ex.empty_i64(nparts);
+    hip::semi_join_mark(ptr<int64_t>(rk), ptr<int64_t>(roffs), ptr<int64_t>(lk), ptr<int64_t>(lrow),
+                        ptr<int64_t>(loffs), nparts, anti, ptr<uint8_t>(mask), ptr<int64_t>(matched),
+                        over.data_ptr<int>(), ptr<int64_t>(ipart), ptr<int64_t>(islice), nitems, ptr<int64_t>(dkeys),
+                        ptr<int64_t>(dmeta), ex.stream);
+  }
+  if (over.item<int>() != 0) {
+    trace::add_counter("join.semi.overflow_fallback", 1);
+    return false;
+  }
+  const int64_t m = matched.item<int64_t>();
+  trace::add_counter("join.semi.matched", m);
+  out->mask = mask;
+  out->invert = false;
+  out->kept = anti ? nl - m : m;
+  return true;
+}
+
+static SemiRows semi_join_rows(const TablePtr &left, const TablePtr &right, const JoinConfig &cfg) {
+  const auto &lc = cfg.GetLeftColumnIdx();
+  const auto &rc = cfg.GetRightColumnIdx();
+  check_join_keys(left, right, cfg);
+  const bool anti = cfg.GetType() == JoinType::LEFT_ANTI;
+  Exec ex(left->device());
+  const int64_t nl = left->Rows(), nr = right->Rows();
+  SemiRows out;
+  if (nl == 0 || nr == 0) {  // nothing matches
+    out.mask = anti ? at::ones({nl}, ex.opts(at::kByte)) : ex.zeros_u8(nl);
+    out.kept = anti ? nl : 0;
+    return out;
+  }
+  // CPU contexts: the twin kernel on a single simple key (radix_keys' composites are device code)
+  const bool simple = lc.size() == 1 && simple_key(left->column(lc[0])) && simple_key(right->column(rc[0])) &&
+                      left->column(lc[0]).type == right->column(rc[0]).type;
+  // device: also integer key columns, nullable or several, that radix_keys may pack into an exact
+  // composite (anything else would only be hashed there, and a hashed image is of no use here)
+  bool packable = lc.size() <= (size_t)kMaxCompositeKeys;
+  for (size_t i = 0; i < lc.size() && packable; ++i) {
+    const Column &a = left->column(lc[i]), &b = right->column(rc[i]);
+    packable = a.type == b.type && (int_key(a) || nullable_int_key(a)) && (int_key(b) || nullable_int_key(b));
+  }
+  if (ex.gpu ? nl >= semi_join_min_rows() && (simple || packable) : simple) {
+    RadixKeys k;
+    if (ex.gpu) {
+      k = radix_keys(ex, left, right, cfg, /*words_ok=*/false);
+    } else {
+      k.l = encode_keys(ex, left, lc, true).keys;
+      k.r = encode_keys(ex, right, rc, true).keys;
+      k.ok = true;
+    }
+    if (k.ok && !k.verify && semi_mark_exact(ex, k.l, k.r, anti, &out)) return out;
+  }
+  trace::add_counter("join.semi.general", 1);
+  std::vector<int> rkeys(rc.size());
+  for (size_t i = 0; i < rc.size(); ++i) rkeys[i] = (int)i;
+  TablePtr rd = Unique(Project(right, rc), rkeys, true);
+  const JoinConfig inner(JoinType::INNER, lc, rkeys, cfg.GetAlgorithm());
+  at::Tensor li = join_impl(left, rd, inner, false, nullptr, nullptr).first;
+  out.mask = ex.zeros_u8(nl);
+  if (li.numel()) KCALL(ex, mark_indices, ptr<int64_t>(li), li.numel(), ptr<uint8_t>(out.mask));
+  out.invert = anti;
+  return out;
+}
+
+static std::pair<at::Tensor, at::Tensor> semi_join_indices(const TablePtr &left, const TablePtr &right,
+                                                           const JoinConfig &cfg) {
+  Exec ex(left->device());
+  SemiRows s = semi_join_rows(left, right, cfg);
+  at::Tensor rows = left->Rows() == 0 ? ex.empty_i64(0) : MaskToIndices(s.mask, s.invert);
+  return {rows, at::full({rows.numel()}, -1, ex.opts(at::kLong))};
+}
+
+static TablePtr semi_join_local(const TablePtr &left, const TablePtr &right, const JoinConfig &cfg) {
+  SemiRows s = semi_join_rows(left, right, cfg);
+  const int64_t nl = left->Rows();
+  CYLON_PHASE("join.materialize", left->device());
+  TablePtr rows;
+  if (s.kept == nl) rows = left;  // every row survives: no compaction, no gather
+  else if (s.kept == 0) rows = Slice(left, 0, 0);
+  else rows = GatherNullable(left, MaskToIndices(s.mask, s.invert), false);
+  std::vector<Column> cols;
+  cols.reserve(rows->Columns());
+  for (const auto &c : rows->columns()) cols.push_back(c.with_name(cfg.GetLeftTablePrefix() + c.name));
+  return Table::Make(left->GetContext(), std::move(cols));
+}
+
 // Local join.  With a sink (chunked distributed join) the radix path writes into
 // the sink and nullptr is returned; other paths return their table.
 static TablePtr join_local(const TablePtr &left, const TablePtr &right, const JoinConfig &cfg, JoinSink *sink) {
+  if (is_semi(cfg.GetType())) return semi_join_local(left, right, cfg);
   const bool big = left->device().is_cuda() && std::min(left->Rows(), right->Rows()) >= radix_join_min_rows();
   const JoinType jt = cfg.GetType();
   if (big && jt == JoinType::INNER && cfg.GetAlgorithm() == JoinAlgorithm::SORT &&
@@ -2202,6 +2370,19 @@ TablePtr Join(const TablePtr &left, const TablePtr &right, const JoinConfig &cfg
 TablePtr DistributedJoin(const TablePtr &left, const TablePtr &right, const JoinConfig &cfg) {
   auto ctx = left->GetContext();
   if (!ctx->ShuffleRequired()) return Join(left, right, cfg);
+  if (is_semi(cfg.GetType())) {
+    // only the right side's key columns travel; equal keys land in the same hash chunk, so the
+    // per-chunk semi / anti joins are exact and their outputs concatenate
+    const auto &rc = cfg.GetRightColumnIdx();
+    std::vector<int> rkeys(rc.size());
+    for (size_t i = 0; i < rc.size(); ++i) rkeys[i] = (int)i;
+    const JoinConfig kcfg(cfg.GetType(), cfg.GetLeftColumnIdx(), rkeys, cfg.GetAlgorithm(), cfg.GetLeftTablePrefix(),
+                          cfg.GetRightTablePrefix());
+    std::vector<TablePtr> parts;
+    ShufflePairPlanned(left, cfg.GetLeftColumnIdx(), Project(right, rc), rkeys,
+                       [&](int, int, const TablePtr &l, const TablePtr &r) { parts.push_back(Join(l, r, kcfg)); });
+    return parts.size() == 1 ? parts[0] : Merge(parts);
+  }
   JoinSink sink;
   TablePtr whole;
   ShufflePairPlanned(left, cfg.GetLeftColumnIdx(), right, cfg.GetRightColumnIdx(),

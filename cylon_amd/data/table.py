@@ -16,7 +16,8 @@ from . import arrow_bridge as ab
 from .table_pandas import PandasOpsMixin
 
 _JOIN_TYPES = {"inner": "inner", "left": "left", "right": "right", "outer": "outer", "full_outer": "outer",
-               "fullouter": "outer"}
+               "fullouter": "outer", "semi": "semi", "left_semi": "semi", "leftsemi": "semi", "anti": "anti",
+               "left_anti": "anti", "leftanti": "anti"}
 
 
 def _ensure_ctx(ctx: Optional[CylonContext]) -> CylonContext:

@@ -37,7 +37,8 @@ int cylon_write_csv(const char *table_id, const char *path);
 int64_t cylon_row_count(const char *table_id);
 int32_t cylon_column_count(const char *table_id);
 int cylon_remove_table(const char *table_id);
-/* join_type: 0 inner, 1 left, 2 right, 3 full outer; algorithm: 0 sort, 1 hash */
+/* join_type: 0 inner, 1 left, 2 right, 3 full outer, 4 left semi, 5 left anti (the last two return
+   the left table's columns only); algorithm: 0 sort, 1 hash */
 int cylon_join(const char *left_id, const char *right_id, int join_type, int algorithm, int left_col,
                int right_col, const char *dest_id);
 int cylon_distributed_join(const char *left_id, const char *right_id, int join_type, int algorithm, int left_col,

@@ -23,7 +23,9 @@ int main(int argc, char **argv) {
   const Kind kinds[] = {{"inner", jc::JoinType::INNER},
                         {"left", jc::JoinType::LEFT},
                         {"right", jc::JoinType::RIGHT},
-                        {"outer", jc::JoinType::FULL_OUTER}};
+                        {"outer", jc::JoinType::FULL_OUTER},
+                        {"semi", jc::JoinType::LEFT_SEMI},  // existence joins: the left table's columns only
+                        {"anti", jc::JoinType::LEFT_ANTI}};
   for (const Kind &k : kinds) {
     int64_t rows[2] = {0, 0};
     for (int a = 0; a < 2; ++a) {

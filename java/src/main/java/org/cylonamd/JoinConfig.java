@@ -2,7 +2,8 @@
 package org.cylonamd;
 
 public final class JoinConfig {
-  public enum Type { INNER, LEFT, RIGHT, FULL_OUTER }
+  // ordinals are the C ABI's join_type values (cylon_capi.h)
+  public enum Type { INNER, LEFT, RIGHT, FULL_OUTER, LEFT_SEMI, LEFT_ANTI }
   public enum Algorithm { SORT, HASH }
 
   final int leftIndex;
