@@ -385,6 +385,16 @@ __global__ void k_ts_offsets(const uint16_t *__restrict__ th, const uint32_t *__
 // with vmcnt(0) for all outstanding loads AND stores: gfx9 counts both on one
 // counter).  Issuing several columns' loads per wait instead (more VGPRs, fewer
 // waves) measured slower -- profiles/rows_pass_experiments_r02.txt.
+//
+// Two column loops.  The general one (partial tiles, every non-slot pass, mixed widths) predicates
+// each row and carries the prefetched column in registers across its back edge; compiled, that
+// carry is a register copy which waits (vmcnt(0)) right after the loads are issued, and the key
+// prefetch is one dependent round trip per row.  Full tiles of slot passes with 8-byte columns
+// -- all but the last tile of every segment -- take a second, unpredicated loop in which the
+// pipelining survives compilation: per column, 8 loads, then the 8 stores of the column before,
+// a barrier, and a counted wait (vmcnt(8): the loads alone) where the loaded column is staged;
+// under the last column the next tile's 8 keys are loaded back to back from clamped addresses.
+// 1B x 1B join: 14.5 -> 12.2 ms per pass (profiles/r07/).
 
 // RANK: kRankBallot (stable wave64 ballot match), kRankBlockAtomic (one LDS atomic per row
 // on block-wide counters: unstable), kRankWaveAtomic (LDS atomics on the wave's own packed
@@ -639,6 +649,94 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(4))) vo
       }
     }
     __syncthreads();  // counters / digits dead: the union becomes the column stage
+    if (SLOT && W8 && cnt == TILE) {
+      // ---- full tile (slot mode, 8-byte columns; uniform branch): every row and every sorted slot
+      // exists, so nothing is predicated, and the loop is rotated -- issue column c+1's loads, drain
+      // column c (stage -> global stores), barrier, stage column c+1 -- so that no loaded register
+      // lives across the back edge (a loop-carried one is copied, and the copy waits for the load
+      // before the drain's stores are even issued).  The loads precede the drain's stores on the
+      // in-order vmcnt, so staging waits for the loads alone (vmcnt(8)) and the stores drain under
+      // the next column.  Slot passes read every column (no row-id column, no next-digit output).
+      const int64_t row0 = tile + wrow + lane;  // this lane's rows: row0 + k * kWave
+      // (the drain and the steps below are straight-line: across a branch between a load and its
+      // wait the compiler's counter bookkeeping falls back to waiting for the stores as well)
+      auto drain = [&](int c, auto n4) {  // n4: column 0 of a narrowing pass, 4-byte offsets
+        uint8_t *out = cols.out[c];
+        if constexpr (decltype(n4)::value) {
+#pragma unroll
+          for (int q = 0; q < kRPItems; ++q)
+            stw<false>(out, (int64_t)dst[q], 4, ldw<false>(st, threadIdx.x + q * THREADS, 4));
+        } else {
+#pragma unroll
+          for (int q = 0; q < kRPItems; ++q)
+            stw<true>(out, (int64_t)dst[q], 8, ldw<true>(st, threadIdx.x + q * THREADS, 8));
+        }
+      };
+      auto step = [&](int c, auto n4) {  // the stage holds column c
+        const uint64_t *in = reinterpret_cast<const uint64_t *>(cols.in[c + 1]) + row0;
+        uint64_t x[kRPItems];
+#pragma unroll
+        for (int k = 0; k < kRPItems; ++k) x[k] = in[k * kWave];
+        drain(c, n4);
+        __syncthreads();  // column c read out of the stage
+#pragma unroll
+        for (int k = 0; k < kRPItems; ++k) stw<true>(st, pl[k], 8, x[k]);
+        __syncthreads();
+      };
+      // last column: the next tile's keys are loaded under its drain, all 8 back to back from
+      // clamped addresses (a row past the next tile's end reads this tile's own row instead);
+      // they are narrowed and range-checked after the drain's stores are issued
+      auto last = [&](auto n4) {
+        next = s_tr0[par ^ 1];
+        const int64_t nrow0 = next + wrow + lane, nend = s_tend[par ^ 1];
+        const int cl = cols.n - 1;
+        if constexpr (Digit::kNarrow) {
+          if (digit.kin4) {
+            const uint32_t *kp = reinterpret_cast<const uint32_t *>(digit.keys);
+#pragma unroll
+            for (int k = 0; k < kRPItems; ++k) kv[k] = kp[(nrow0 + k * kWave < nend ? nrow0 : row0) + k * kWave];
+            drain(cl, n4);
+#pragma unroll
+            for (int k = 0; k < kRPItems; ++k) asm volatile("" : "+v"(kv[k]));  // the counted wait sits here, in the branch
+          } else {
+            const int64_t *kp = reinterpret_cast<const int64_t *>(digit.keys);
+            uint64_t r[kRPItems];
+#pragma unroll
+            for (int k = 0; k < kRPItems; ++k)
+              r[k] = (uint64_t)kp[(nrow0 + k * kWave < nend ? nrow0 : row0) + k * kWave];
+            drain(cl, n4);
+#pragma unroll
+            for (int k = 0; k < kRPItems; ++k) {
+              narrow_bad |= nrow0 + k * kWave < nend && digit.too_wide(r[k]);
+              kv[k] = (KVT)digit.narrow(r[k]);
+            }
+          }
+        } else {
+#pragma unroll
+          for (int k = 0; k < kRPItems; ++k)
+            kv[k] = (KVT)digit.key_at((nrow0 + k * kWave < nend ? nrow0 : row0) + k * kWave);
+          drain(cl, n4);
+        }
+        __syncthreads();
+      };
+      using N4 = std::integral_constant<bool, Digit::kNarrow>;
+      if constexpr (Digit::kNarrow) {
+#pragma unroll
+        for (int k = 0; k < kRPItems; ++k) stw<false>(st, pl[k], 4, (uint64_t)kv[k]);
+      } else {
+#pragma unroll
+        for (int k = 0; k < kRPItems; ++k) stw<true>(st, pl[k], 8, (uint64_t)kv[k] ^ cols.key_xor);
+      }
+      __syncthreads();
+      if (cols.n == 1) {
+        last(N4{});
+      } else {
+        step(0, N4{});
+#pragma unroll 1
+        for (int c = 1; c + 1 < cols.n; ++c) step(c, std::false_type{});
+        last(std::false_type{});
+      }
+    } else {
     // load column c+1 while column c streams out of the stage
     uint64_t v[kRPItems];
 #pragma unroll
@@ -708,6 +806,7 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(4))) vo
       }
       __syncthreads();
     }
+    }  // (partial tile)
 #undef RP_DEST
     if (!TICKET)
       for (uint32_t p = threadIdx.x; p < nbuckets; p += blockDim.x) running[p] += toff[p + 1] - toff[p];
