@@ -46,7 +46,7 @@ def capi_library() -> ctypes.CDLL:
         "cylon_row_count": ([s], i64), "cylon_column_count": ([s], ctypes.c_int32),
         "cylon_remove_table": ([s], i), "cylon_join": ([s, s, i, i, i, i, s], i),
         "cylon_distributed_join": ([s, s, i, i, i, i, s], i), "cylon_set_op": ([s, s, i, i, s], i),
-        "cylon_sort": ([s, i, i, s], i), "cylon_project": ([s, ctypes.POINTER(ctypes.c_int32), i, s], i),
+        "cylon_sort": ([s, i, i, s], i), "cylon_topk": ([s, i, i, i64, s], i), "cylon_project": ([s, ctypes.POINTER(ctypes.c_int32), i, s], i),
     }
     pp = ctypes.POINTER
     sig.update({

@@ -291,6 +291,9 @@ void register_extended_ops(py::module &m) {
         return ops::DistributedSort(t, cols, asc, o);
       },
       rel);
+  m.def("topk", &ops::TopK, py::arg("table"), py::arg("cols"), py::arg("ascending"), py::arg("k"), rel);
+  m.def("distributed_topk", &ops::DistributedTopK, py::arg("table"), py::arg("cols"), py::arg("ascending"),
+        py::arg("k"), rel);
   // ---- streaming op graph (C24) ------------------------------------------
   m.def(
       "dis_join_op",

@@ -161,6 +161,10 @@ CYLON_CAPI int cylon_sort(const char *id, int column, int ascending, const char 
   return guard([&] { return status(SortTable(id, column, dest, ascending != 0)); });
 }
 
+CYLON_CAPI int cylon_topk(const char *id, int column, int ascending, int64_t k, const char *dest) {
+  return guard([&] { return status(TopKTable(id, column, k, dest, ascending != 0)); });
+}
+
 CYLON_CAPI int cylon_project(const char *id, const int32_t *cols, int n, const char *dest) {
   return guard([&] {
     TablePtr out;

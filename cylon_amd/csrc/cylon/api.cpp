@@ -81,6 +81,14 @@ Status DistributedSort(const TablePtr &t, const std::vector<int32_t> &cols, Tabl
                        const std::vector<bool> &dirs, SortOptions opts) {
   return guard([&] { out = ops::DistributedSort(t, std::vector<int>(cols.begin(), cols.end()), dirs, opts); });
 }
+Status TopK(const TablePtr &t, const std::vector<int32_t> &cols, int64_t k, TablePtr &out,
+            const std::vector<bool> &dirs) {
+  return guard([&] { out = ops::TopK(t, std::vector<int>(cols.begin(), cols.end()), dirs, k); });
+}
+Status DistributedTopK(const TablePtr &t, const std::vector<int32_t> &cols, int64_t k, TablePtr &out,
+                       const std::vector<bool> &dirs) {
+  return guard([&] { out = ops::DistributedTopK(t, std::vector<int>(cols.begin(), cols.end()), dirs, k); });
+}
 Status Shuffle(const TablePtr &t, const std::vector<int> &cols, TablePtr &out) {
   return guard([&] { out = ops::Shuffle(t, cols); });
 }
@@ -267,6 +275,9 @@ Status UnionTables(const std::string &a, const std::string &b, const std::string
 
 Status SortTable(const std::string &id, int col, const std::string &dest, bool asc) {
   return guard([&] { PutTable(dest, ops::Sort(GetTable(id), {col}, {asc})); });
+}
+Status TopKTable(const std::string &id, int col, int64_t k, const std::string &dest, bool asc) {
+  return guard([&] { PutTable(dest, ops::TopK(GetTable(id), {col}, {asc}, k)); });
 }
 
 int64_t RowCount(const std::string &id) { return GetTable(id)->Rows(); }

@@ -55,6 +55,11 @@ Status Sort(const TablePtr &t, int sort_column, TablePtr &out, bool ascending = 
 Status Sort(const TablePtr &t, const std::vector<int32_t> &cols, TablePtr &out, const std::vector<bool> &dirs);
 Status DistributedSort(const TablePtr &t, const std::vector<int32_t> &cols, TablePtr &out,
                        const std::vector<bool> &dirs, SortOptions opts = SortOptions::Defaults());
+// ORDER BY cols LIMIT k: the first min(k, rows) rows of the stable sort (docs/semantics.md "Top-k")
+Status TopK(const TablePtr &t, const std::vector<int32_t> &cols, int64_t k, TablePtr &out,
+            const std::vector<bool> &dirs);
+Status DistributedTopK(const TablePtr &t, const std::vector<int32_t> &cols, int64_t k, TablePtr &out,
+                       const std::vector<bool> &dirs);
 Status Shuffle(const TablePtr &t, const std::vector<int> &hash_cols, TablePtr &out);
 Status HashPartition(const TablePtr &t, const std::vector<int> &hash_cols, int num_partitions,
                      std::map<int, TablePtr> *out);
@@ -144,6 +149,7 @@ Status DistributedJoinTables(const std::string &left_id, const std::string &righ
                              const join::config::JoinConfig &cfg, const std::string &dest_id);
 Status UnionTables(const std::string &a, const std::string &b, const std::string &dest, bool distributed);
 Status SortTable(const std::string &id, int col, const std::string &dest, bool ascending);
+Status TopKTable(const std::string &id, int col, int64_t k, const std::string &dest, bool ascending);
 int64_t RowCount(const std::string &id);
 int32_t ColumnCount(const std::string &id);
 std::vector<std::string> ColumnNames(const std::string &id);

@@ -407,6 +407,26 @@ void semi_join_mark(const int64_t *rkeys, const int64_t *roffs, const int64_t *l
                     const int64_t *loffs, int64_t nparts, int anti, uint8_t *mask, int64_t *matched, int *overflow,
                     const int64_t *ipart, const int64_t *islice, int64_t nitems, int64_t *dkeys, int64_t *dmeta,
                     void *stream);
+/* Top-k radix select over a fixed-width column's sort image (topk.hip; CPU twin cpu_topk.cpp; the
+   image is order_image.hpp sort_key_image; null rows take no part).  ws: topk_workspace() int64 words,
+   the first topk_state_words() of them the state (topk.hip TKState) that the operator reads back.
+   topk_scan: clears ws; OR / AND of the images and the non-null count.
+   topk_start: select k_rem = k rows from bits [.., ihi) of the image, then [.., rhi) of the row number.
+   topk_hist: histogram of the next db (<= topk_digit_bits()) undecided bits of the image (src 0) or
+   the row number (src 1) over the rows whose decided bits equal the prefix; topk_pick: the bin where
+   the running count crosses k_rem -> prefix, k_rem, sure, bucket; zeroes the histogram.
+   topk_collect: (image, row) of the rows below the prefix -> sure list, equal to it -> candidate
+   list, in any order; a list that outgrows its capacity sets the state's error word, nothing is
+   written past it. */
+int topk_digit_bits();
+int64_t topk_state_words();
+int64_t topk_workspace();
+void topk_scan(const ColView &col, int64_t n, bool desc, int64_t *ws, void *stream);
+void topk_start(int64_t *ws, int64_t k, int ihi, int rhi, void *stream);
+void topk_hist(const ColView &col, int64_t n, bool desc, int64_t *ws, int src, int db, void *stream);
+void topk_pick(int64_t *ws, int src, int db, void *stream);
+void topk_collect(const ColView &col, int64_t n, bool desc, int64_t *ws, uint64_t *sure_img, int64_t *sure_row,
+                  int64_t sure_cap, uint64_t *cand_img, int64_t *cand_row, int64_t cand_cap, void *stream);
 /* shuffle wire format: int64 values shipped as uint32 offsets from a global base (range < 2^32) */
 void narrow_i64(const int64_t *in, int64_t n, int64_t base, uint32_t *out, void *stream);
 void widen_u32(const uint32_t *in, int64_t n, int64_t base, int64_t *out, void *stream);

@@ -18,6 +18,7 @@
 //   * merge join: per left key a lower/upper bound search in the sorted right
 //     keys (count pass stores the lower bound), scan, and a write pass that
 //     expands the equal range into (left row, right row) pairs.
+#include "order_image.hpp"
 #include "radix_pass.hpp"
 
 namespace cylon {
@@ -26,28 +27,7 @@ namespace hip {
 // ---------------------------------------------------------------------------
 // key images
 // ---------------------------------------------------------------------------
-__device__ __forceinline__ uint64_t order_image(uint64_t bits, int w, int kind) {
-  const int nb = 8 * w;
-  const uint64_t mask = (nb == 64) ? ~0ull : ((1ull << nb) - 1);
-  const uint64_t sign = 1ull << (nb - 1);
-  bits &= mask;
-  if (kind == static_cast<int>(ValueKind::SIGNED_INT)) return bits ^ sign;
-  if (kind == static_cast<int>(ValueKind::FLOAT)) {
-    // canonicalise -0.0 to +0.0 and every NaN to the positive quiet NaN (sorts last)
-    if (bits == sign) bits = 0;
-    const uint64_t exp_mask = (w == 8) ? 0x7ff0000000000000ull : (w == 4 ? 0x7f800000ull : 0x7c00ull);
-    const uint64_t man_mask = (w == 8) ? 0x000fffffffffffffull : (w == 4 ? 0x007fffffull : 0x03ffull);
-    if ((bits & exp_mask) == exp_mask && (bits & man_mask) != 0) bits = exp_mask | ((man_mask + 1) >> 1);
-    return (bits & sign) ? (~bits & mask) : (bits | sign);
-  }
-  return bits;
-}
-
-__device__ __forceinline__ bool is_nan_bits(uint64_t bits, int w) {
-  if (w == 8) return (bits & 0x7ff0000000000000ull) == 0x7ff0000000000000ull && (bits & 0x000fffffffffffffull);
-  if (w == 4) return (bits & 0x7f800000ull) == 0x7f800000ull && (bits & 0x007fffffull);
-  return (bits & 0x7c00ull) == 0x7c00ull && (bits & 0x03ffull);
-}
+// order_image / is_nan_bits / sort_key_image: order_image.hpp (shared with the top-k select)
 
 // acc != nullptr: also OR / AND-reduce the images into acc[0] / acc[1] (the bits
 // that vary, for the radix pass count) so the sort needs no second read of them
@@ -60,9 +40,7 @@ __global__ void k_sort_keys(ColView c, const int64_t *__restrict__ perm, int64_t
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
     const int64_t s = perm ? perm[i] : i;
     const uint64_t bits = load_bits(c.data, s, c.width);
-    uint64_t k = order_image(bits, c.width, c.kind);
-    if (desc) k = ~k & mask;
-    if (c.kind == static_cast<int>(ValueKind::FLOAT) && is_nan_bits(bits, c.width)) k = mask;  // NaN last
+    uint64_t k = sort_key_image(bits, c.width, c.kind, desc);  // NaN last in both directions
     // a null's image is a constant: null rows keep their order from the previous (less
     // significant) sort columns, so equal rows stay adjacent in multi-column sorts
     if (c.valid != nullptr && c.valid[s] == 0) k = mask;

@@ -178,6 +178,12 @@ void SetPartitionDigitBits(int bits);
 at::Tensor SortIndices(const TablePtr &t, const std::vector<int> &cols, const std::vector<bool> &ascending,
                        bool grouping = false);
 TablePtr Sort(const TablePtr &t, const std::vector<int> &cols, const std::vector<bool> &ascending);
+// ORDER BY cols LIMIT k (ops/topk.cpp): the rows, and the row order, of the first min(k, rows) rows
+// of the stable index sort.  DistributedTopK: the global k rows on rank 0 (ties by rank, then row),
+// an empty table with the same schema on every other rank.
+TablePtr TopK(const TablePtr &t, const std::vector<int> &cols, const std::vector<bool> &ascending, int64_t k);
+TablePtr DistributedTopK(const TablePtr &t, const std::vector<int> &cols, const std::vector<bool> &ascending,
+                         int64_t k);
 
 }  // namespace ops
 }  // namespace cylon

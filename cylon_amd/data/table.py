@@ -346,6 +346,29 @@ class Table(PandasOpsMixin):
         asc = [bool(a) for a in ascending] if isinstance(ascending, (list, tuple)) else [bool(ascending)]
         return self._wrap(C.sort(self._t, cols, asc))
 
+    def _topk_args(self, k, order_by, ascending):
+        if int(k) < 0:
+            raise ValueError(f"top-k needs k >= 0, got {k}")
+        cols = self._resolve_columns(order_by if order_by is not None else 0)
+        asc = [bool(a) for a in ascending] if isinstance(ascending, (list, tuple)) else [bool(ascending)] * len(cols)
+        return cols, asc, int(k)
+
+    def topk(self, k: int, order_by=None, ascending: Union[bool, List[bool]] = True) -> "Table":
+        """ORDER BY order_by LIMIT k: the first min(k, rows) rows of the stable sort, all columns.
+        Ties at the cut keep the lower row number; NaN sorts after every number and null after NaN
+        in both directions (docs/semantics.md "Top-k")."""
+        return self._wrap(C.topk(self._t, *self._topk_args(k, order_by, ascending)))
+
+    def distributed_topk(self, k: int, order_by=None, ascending: Union[bool, List[bool]] = True) -> "Table":
+        """The global top k rows on rank 0 (ties by rank, then row); 0 rows on every other rank."""
+        return self._wrap(C.distributed_topk(self._t, *self._topk_args(k, order_by, ascending)))
+
+    def nlargest(self, n: int, columns) -> "Table":
+        return self.topk(n, columns, ascending=False)
+
+    def nsmallest(self, n: int, columns) -> "Table":
+        return self.topk(n, columns, ascending=True)
+
     def shuffle(self, hash_columns: List = None) -> "Table":
         return self._wrap(C.shuffle(self._t, self._resolve_columns(hash_columns)))
 

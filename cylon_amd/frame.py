@@ -387,6 +387,21 @@ class DataFrame(object):
             return DataFrame(self._table.sort(order_by=by, ascending=ascending))
         return DataFrame(self._change_context(env)._table.distributed_sort(order_by=by, ascending=ascending))
 
+    def _n_extreme(self, n, columns, keep, largest: bool, env) -> "DataFrame":
+        if keep != "first":
+            raise NotImplementedError(f"keep='{keep}': only keep='first' (the lower row number wins a tie)")
+        if env is None:
+            return DataFrame(self._table.topk(n, columns, ascending=not largest))
+        return DataFrame(self._change_context(env)._table.distributed_topk(n, columns, ascending=not largest))
+
+    def nlargest(self, n: int, columns, keep: str = "first", env: CylonEnv = None) -> "DataFrame":
+        """The n rows with the largest values in `columns`, largest first (pandas nlargest, keep='first').
+        With env: the global rows, on rank 0."""
+        return self._n_extreme(n, columns, keep, True, env)
+
+    def nsmallest(self, n: int, columns, keep: str = "first", env: CylonEnv = None) -> "DataFrame":
+        return self._n_extreme(n, columns, keep, False, env)
+
     def groupby(self, by, agg: dict, algorithm: str = "hash", env: CylonEnv = None) -> "DataFrame":
         if env is None:
             return DataFrame(self._table.local_groupby(by, agg, algorithm))

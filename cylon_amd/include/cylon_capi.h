@@ -46,6 +46,8 @@ int cylon_distributed_join(const char *left_id, const char *right_id, int join_t
 /* set ops: op 0 union, 1 subtract, 2 intersect */
 int cylon_set_op(const char *a_id, const char *b_id, int op, int distributed, const char *dest_id);
 int cylon_sort(const char *table_id, int column, int ascending, const char *dest_id);
+/* ORDER BY column LIMIT k: the first min(k, rows) rows of the stable sort; k < 0 is an error */
+int cylon_topk(const char *table_id, int column, int ascending, int64_t k, const char *dest_id);
 int cylon_project(const char *table_id, const int32_t *columns, int ncolumns, const char *dest_id);
 
 int cylon_merge(const char *const *table_ids, int ntables, const char *dest_id);

@@ -51,6 +51,14 @@ def distributed_sort(t: Table, order_by=None, ascending: Union[bool, List[bool]]
     return t.distributed_sort(order_by, ascending, sort_options)
 
 
+def topk(t: Table, k: int, order_by=None, ascending: Union[bool, List[bool]] = True) -> Table:
+    return t.topk(k, order_by, ascending)
+
+
+def distributed_topk(t: Table, k: int, order_by=None, ascending: Union[bool, List[bool]] = True) -> Table:
+    return t.distributed_topk(k, order_by, ascending)
+
+
 def shuffle(t: Table, hash_columns: List = None) -> Table:
     return t.shuffle(hash_columns)
 
@@ -85,5 +93,6 @@ def merge(tables: Sequence[Table]) -> Table:
 
 
 __all__ = ["join", "distributed_join", "union", "subtract", "intersect", "distributed_union",
-           "distributed_subtract", "distributed_intersect", "sort", "distributed_sort", "shuffle",
+           "distributed_subtract", "distributed_intersect", "sort", "distributed_sort", "topk",
+           "distributed_topk", "shuffle",
            "hash_partition", "unique", "distributed_unique", "groupby", "local_groupby", "project", "merge"]

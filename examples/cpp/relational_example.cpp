@@ -52,7 +52,7 @@ int main(int argc, char **argv) {
     return p;
   };
 
-  TablePtr a, b, j, js, u, i, s, q, srt, g, sum, back;
+  TablePtr a, b, j, js, u, i, s, q, srt, top, g, sum, back;
   CHECK_OK(cylon::FromCSV(ctx, path(argv[2]), a));
   CHECK_OK(cylon::FromCSV(ctx, path(argv[3]), b, cylon::io::CSVReadOptions().WithDelimiter(',').UseThreads(true).BlockSize(1 << 20)));
   report("left", a);
@@ -74,6 +74,8 @@ int main(int argc, char **argv) {
 
   CHECK_OK(cylon::Sort(a, 0, srt, true));
   report("sort", srt);
+  CHECK_OK(cylon::TopK(a, {0}, 5, top, {false}));  // ORDER BY column 0 DESC LIMIT 5
+  report("topk", top);
   CHECK_OK(cylon::DistributedHashGroupBy(a, {0}, {1}, {cylon::AGG_SUM}, g));
   report("groupby_sum", g);
   CHECK_OK(cylon::compute::Sum(a, 1, sum));
