@@ -92,11 +92,30 @@ c10d::ProcessGroup &ProcessGroupCommunicator::pg() const {
   return *pg_;
 }
 
+// bool, int16 and the unsigned 16 / 32 / 64-bit types are not collective dtypes on every backend
+// (gloo and RCCL refuse them).  A collective that only moves data carries them as a type of the
+// same width, so counts and offsets in elements stay what they are; a reduction (which computes
+// with the values) only gives bool as bytes.
+static at::ScalarType wire_dtype(at::ScalarType t, bool moves_only) {
+  if (t == at::kBool) return at::kByte;
+  if (!moves_only) return t;
+  switch (t) {
+    case at::kShort:
+    case at::kUInt16: return at::kHalf;
+    case at::kUInt32: return at::kInt;
+    case at::kUInt64: return at::kLong;
+    default: return t;
+  }
+}
+
+static at::Tensor wire_view(const at::Tensor &t, bool moves_only = true) {
+  const at::ScalarType w = wire_dtype(t.scalar_type(), moves_only);
+  return w == t.scalar_type() ? t : t.view(w);
+}
+
 at::Tensor ProcessGroupCommunicator::to_comm(const at::Tensor &t) const {
   at::Tensor c = t.device() == device_ ? t : t.to(device_);
-  // bool is not a collective dtype on every backend; move it as bytes
-  if (c.scalar_type() == at::kBool) c = c.view(at::kByte);
-  return c.contiguous();
+  return wire_view(c).contiguous();
 }
 
 void ProcessGroupCommunicator::Barrier() {
@@ -123,7 +142,7 @@ at::Tensor ProcessGroupCommunicator::AllToAllV(const at::Tensor &send, const std
   at::Tensor out = at::empty(shape, in.options());
   std::vector<int64_t> sc(send_counts), rc(recv_counts);
   wait_work(pg().alltoall_base(out, in, rc, sc));
-  if (send.scalar_type() == at::kBool) out = out.view(at::kBool);
+  if (out.scalar_type() != send.scalar_type()) out = out.view(send.scalar_type());
   return out.device() == send.device() ? out : out.to(send.device());
 }
 
@@ -150,7 +169,7 @@ static c10d::ReduceOp to_c10d(ReduceOp op) {
 
 void ProcessGroupCommunicator::AllReduce(at::Tensor &t, ReduceOp op) {
   trace::add_counter("comm.allreduce", 1);
-  at::Tensor c = to_comm(t);
+  at::Tensor c = wire_view(t.device() == device_ ? t : t.to(device_), false).contiguous();
   std::vector<at::Tensor> v{c};
   c10d::AllreduceOptions o;
   o.reduceOp = to_c10d(op);
@@ -168,7 +187,7 @@ at::Tensor ProcessGroupCommunicator::AllGather(const at::Tensor &in) {
   at::Tensor out = at::empty(shape, c.options());
   at::Tensor src = c.dim() == 0 ? c.reshape({1}) : c;
   wait_work(pg()._allgather_base(out, src));
-  if (in.scalar_type() == at::kBool) out = out.view(at::kBool);
+  if (out.scalar_type() != in.scalar_type()) out = out.view(in.scalar_type());
   return out.device() == in.device() ? out : out.to(in.device());
 }
 
@@ -317,7 +336,7 @@ std::pair<at::Tensor, std::shared_ptr<P2PRequest>> ProcessGroupCommunicator::All
   auto work = pg().alltoall_base(out, in, rc, sc);
   // the receive buffer is handed out in the caller's dtype/device once waited on
   at::Tensor user = out;
-  if (send.scalar_type() == at::kBool) user = out.view(at::kBool);
+  if (out.scalar_type() != send.scalar_type()) user = out.view(send.scalar_type());
   if (user.device() != send.device()) {
     auto req = std::make_shared<PGRequest>(work, out, at::Tensor(), type_ != CommType::RCCL);
     req->Wait();
@@ -345,8 +364,7 @@ std::shared_ptr<P2PRequest> ProcessGroupCommunicator::AllToAllVSegmentsAsync(
   CYLON_CHECK(send.is_contiguous() && recv.is_contiguous() && send.scalar_type() == recv.scalar_type(),
               Code::Invalid, "segment all-to-all: contiguous buffers of one dtype");
   trace::add_counter("comm.alltoall_posted", 1);
-  at::Tensor s = send.scalar_type() == at::kBool ? send.view(at::kByte) : send;
-  at::Tensor d = recv.scalar_type() == at::kBool ? recv.view(at::kByte) : recv;
+  at::Tensor s = wire_view(send), d = wire_view(recv);
   std::vector<at::Tensor> in, out;
   for (int r = 0; r < world_; ++r) {
     in.push_back(s.slice(0, soff[r], soff[r] + scnt[r]));

@@ -9,7 +9,9 @@
 // Differences by design (documented in docs/semantics.md):
 //   * every decomposable op (SUM, COUNT, MIN, MAX, MEAN, VAR, STDDEV) is
 //     combined locally before the shuffle through partial states
-//     (count, sum, M2, sum^2/count), so only #local-groups rows cross xGMI;
+//     (count, sum, M2 about the partial's own mean), so only #local-groups
+//     rows cross xGMI; the M2 states merge by Chan's pairwise update about the
+//     group mean (no difference of two sums of squares);
 //   * output names carry a single prefix (the reference double-prefixes in
 //     its two-phase path);
 //   * COUNT counts non-null values (identical to the reference on non-null data).
@@ -1002,10 +1004,12 @@ TablePtr DistributedHashGroupBy(const TablePtr &t, const std::vector<int> &keys,
   // are their own partial states, so the local hash group-by produces them directly
   // (the LDS radix group-by on device tables, radix_groupby.hip) instead of the
   // global group-id path below.
+  // (MEAN of an integer column is not: its SUM is an int64 that wraps where the float64 sum of
+  // the local MEAN does not, so it takes the generic form's float64 sum state.)
   bool simple_states = true;
   for (const auto &a : aggs)
     simple_states &= (a.op == AGG_SUM || a.op == AGG_COUNT || a.op == AGG_MIN || a.op == AGG_MAX ||
-                      a.op == AGG_MEAN) &&
+                      (a.op == AGG_MEAN && t->column(a.col).type.kind() == ValueKind::FLOAT)) &&
                      !t->column(a.col).nullable();
   if (simple_states) {
     std::vector<AggSpec> st;
@@ -1054,16 +1058,13 @@ TablePtr DistributedHashGroupBy(const TablePtr &t, const std::vector<int> &keys,
         add_state(p, double_col("", acc.run(c, kSumF)), AGG_SUM);
         add_state(p, long_col("", acc.run(c, kCount)), AGG_SUM);
         break;
-      default: {  // VAR / STDDEV: (count, sum, M2, sum^2/count)
+      default: {  // VAR / STDDEV: (count, sum, M2 about this partial's mean)
         at::Tensor s = acc.run(c, kSumF), n = acc.run(c, kCount);
-        at::Tensor nd = n.to(at::kDouble);
-        at::Tensor mean = (s / nd).contiguous();
+        at::Tensor mean = (s / n.to(at::kDouble)).contiguous();
         at::Tensor m2 = at::nan_to_num(acc.run(c, kM2, mean), 0.0);
-        at::Tensor q = at::nan_to_num(s * s / nd, 0.0);
         add_state(p, long_col("", n), AGG_SUM);
         add_state(p, double_col("", s), AGG_SUM);
         add_state(p, double_col("", m2), AGG_SUM);
-        add_state(p, double_col("", q), AGG_SUM);
       }
     }
     plans.push_back(std::move(p));
@@ -1072,9 +1073,35 @@ TablePtr DistributedHashGroupBy(const TablePtr &t, const std::vector<int> &keys,
   }  // generic phase 1
   // phase 2: shuffle partial rows by key and combine -- chunk by hash-disjoint chunk, so the
   // combine of chunk k runs while the later chunks are still on the wire
+  bool has_m2 = false;
+  for (const auto &p : plans) has_m2 |= p.op == AGG_VAR || p.op == AGG_STDDEV;
   std::vector<TablePtr> combined;
   ShufflePlanned(partial, key_pos, [&](int, int, const TablePtr &sh) {
-    combined.push_back(HashGroupBy(sh, key_pos, combine));
+    if (!has_m2) {
+      combined.push_back(HashGroupBy(sh, key_pos, combine));
+      return;
+    }
+    // VAR / STDDEV: every partial row of a group is on this rank now.  Its states merge as
+    //   M2 = sum_i m2_i + sum_i n_i * (s_i / n_i - mean)^2,   mean = sum_i s_i / sum_i n_i
+    // (Chan's update about the group mean): each term is >= 0 and of the size of M2 itself, where
+    // sum_i s_i^2 / n_i - n * mean^2 cancels two numbers of size n * mean^2.  The group ids of the
+    // partial rows carry the group mean back to them.
+    Exec ex(sh->device());
+    GroupInfo gi = GroupIds(sh, key_pos, false);
+    std::vector<Column> cols = GatherNullable(Project(sh, key_pos), gi.first_rows, false)->columns();
+    for (const auto &a : combine) cols.push_back(agg_column(ex, sh, gi, a));
+    Acc acc{ex, gi.gid, sh->Rows(), gi.ngroups};
+    for (const auto &p : plans) {
+      if (p.op != AGG_VAR && p.op != AGG_STDDEV) continue;
+      const int np = p.state_cols[0], sp = p.state_cols[1], mp = p.state_cols[2];
+      at::Tensor mean = cols[sp].data / cols[np].data.to(at::kDouble);
+      at::Tensor ni = sh->column(np).data.view(at::kLong).slice(0, 0, sh->Rows()).to(at::kDouble);
+      at::Tensor si = sh->column(sp).data.view(at::kDouble).slice(0, 0, sh->Rows());
+      at::Tensor d = si / ni - mean.index_select(0, gi.gid);
+      at::Tensor cross = at::nan_to_num(ni * d * d, 0.0);  // (a partial without values: 0 * NaN)
+      cols[mp] = double_col(cols[mp].name, cols[mp].data + acc.run(double_col("", cross), kSumF));
+    }
+    combined.push_back(Table::Make(sh->GetContext(), std::move(cols)));
   });
   TablePtr comb = combined.size() == 1 ? combined[0] : Merge(combined);
   std::vector<Column> out;
@@ -1095,12 +1122,8 @@ TablePtr DistributedHashGroupBy(const TablePtr &t, const std::vector<int> &keys,
       }
       default: {
         at::Tensor n = comb->column(ci++).data.to(at::kDouble);
-        at::Tensor s = comb->column(ci++).data;
-        at::Tensor m2 = comb->column(ci++).data;
-        at::Tensor q = comb->column(ci++).data;
-        at::Tensor mean = s / n;
-        at::Tensor M2 = at::clamp_min(m2 + q - n * mean * mean, 0.0);
-        at::Tensor var = M2 / (n - p.ddof);
+        ci++;  // (the sum: used by the combine)
+        at::Tensor var = comb->column(ci++).data / (n - p.ddof);
         out.push_back(double_col(p.name, p.op == AGG_VAR ? var : var.sqrt(), (n - p.ddof) > 0));
       }
     }
