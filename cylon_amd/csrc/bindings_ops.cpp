@@ -294,6 +294,40 @@ void register_extended_ops(py::module &m) {
   m.def("topk", &ops::TopK, py::arg("table"), py::arg("cols"), py::arg("ascending"), py::arg("k"), rel);
   m.def("distributed_topk", &ops::DistributedTopK, py::arg("table"), py::arg("cols"), py::arg("ascending"),
         py::arg("k"), rel);
+  // window functions: specs as flat lists (WindowFunc numbers, value columns, LAG / LEAD offsets, output names)
+  auto window_specs = [](const std::vector<int> &funcs, const std::vector<int> &cols, const std::vector<int64_t> &args,
+                         const std::vector<std::string> &names) {
+    CYLON_CHECK(funcs.size() == cols.size() && funcs.size() == args.size() && funcs.size() == names.size(),
+                Code::Invalid, "window spec lists differ in length");
+    std::vector<WindowSpec> specs;
+    for (size_t i = 0; i < funcs.size(); ++i) {
+      CYLON_CHECK(funcs[i] >= WIN_ROW_NUMBER && funcs[i] <= WIN_LEAD, Code::Invalid, "window function " << funcs[i]);
+      specs.push_back({static_cast<WindowFunc>(funcs[i]), cols[i], args[i], names[i]});
+    }
+    return specs;
+  };
+  m.def(
+      "window",
+      [window_specs](const TablePtr &t, const std::vector<int> &part, const std::vector<int> &order,
+                     const std::vector<bool> &asc, const std::vector<int> &funcs, const std::vector<int> &cols,
+                     const std::vector<int64_t> &args, const std::vector<std::string> &names, int64_t carry_step_tiles) {
+        return ops::Window(t, part, order, asc, window_specs(funcs, cols, args, names), carry_step_tiles);
+      },
+      py::arg("table"), py::arg("partition_cols"), py::arg("order_cols"), py::arg("ascending"), py::arg("funcs"),
+      py::arg("cols"), py::arg("args"), py::arg("names"), py::arg("carry_step_tiles") = 0, rel);
+  m.def(
+      "distributed_window",
+      [window_specs](const TablePtr &t, const std::vector<int> &part, const std::vector<int> &order,
+                     const std::vector<bool> &asc, const std::vector<int> &funcs, const std::vector<int> &cols,
+                     const std::vector<int64_t> &args, const std::vector<std::string> &names) {
+        return ops::DistributedWindow(t, part, order, asc, window_specs(funcs, cols, args, names));
+      },
+      py::arg("table"), py::arg("partition_cols"), py::arg("order_cols"), py::arg("ascending"), py::arg("funcs"),
+      py::arg("cols"), py::arg("args"), py::arg("names"), rel);
+  // rows per tile of the window scans and tiles per step of their carry scan (kernels/window.hip); the
+  // CPU twin is one sequential loop and reports the same numbers
+  m.def("window_tile_rows", []() { return hip::window_tile_rows(); });
+  m.def("window_carry_tiles", []() { return hip::window_carry_tiles(); });
   // ---- streaming op graph (C24) ------------------------------------------
   m.def(
       "dis_join_op",

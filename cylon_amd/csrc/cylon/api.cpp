@@ -89,6 +89,21 @@ Status DistributedTopK(const TablePtr &t, const std::vector<int32_t> &cols, int6
                        const std::vector<bool> &dirs) {
   return guard([&] { out = ops::DistributedTopK(t, std::vector<int>(cols.begin(), cols.end()), dirs, k); });
 }
+Status Window(const TablePtr &t, const std::vector<int32_t> &partition_cols, const std::vector<int32_t> &order_cols,
+              const std::vector<bool> &dirs, const std::vector<WindowSpec> &specs, TablePtr &out) {
+  return guard([&] {
+    out = ops::Window(t, std::vector<int>(partition_cols.begin(), partition_cols.end()),
+                      std::vector<int>(order_cols.begin(), order_cols.end()), dirs, specs);
+  });
+}
+Status DistributedWindow(const TablePtr &t, const std::vector<int32_t> &partition_cols,
+                         const std::vector<int32_t> &order_cols, const std::vector<bool> &dirs,
+                         const std::vector<WindowSpec> &specs, TablePtr &out) {
+  return guard([&] {
+    out = ops::DistributedWindow(t, std::vector<int>(partition_cols.begin(), partition_cols.end()),
+                                 std::vector<int>(order_cols.begin(), order_cols.end()), dirs, specs);
+  });
+}
 Status Shuffle(const TablePtr &t, const std::vector<int> &cols, TablePtr &out) {
   return guard([&] { out = ops::Shuffle(t, cols); });
 }
@@ -278,6 +293,16 @@ Status SortTable(const std::string &id, int col, const std::string &dest, bool a
 }
 Status TopKTable(const std::string &id, int col, int64_t k, const std::string &dest, bool asc) {
   return guard([&] { PutTable(dest, ops::TopK(GetTable(id), {col}, {asc}, k)); });
+}
+Status WindowTable(const std::string &id, const std::vector<int32_t> &partition_cols,
+                   const std::vector<int32_t> &order_cols, const std::vector<bool> &dirs,
+                   const std::vector<WindowSpec> &specs, const std::string &dest, bool distributed) {
+  return guard([&] {
+    const std::vector<int> part(partition_cols.begin(), partition_cols.end());
+    const std::vector<int> order(order_cols.begin(), order_cols.end());
+    PutTable(dest, distributed ? ops::DistributedWindow(GetTable(id), part, order, dirs, specs)
+                               : ops::Window(GetTable(id), part, order, dirs, specs));
+  });
 }
 
 int64_t RowCount(const std::string &id) { return GetTable(id)->Rows(); }

@@ -60,6 +60,13 @@ Status TopK(const TablePtr &t, const std::vector<int32_t> &cols, int64_t k, Tabl
             const std::vector<bool> &dirs);
 Status DistributedTopK(const TablePtr &t, const std::vector<int32_t> &cols, int64_t k, TablePtr &out,
                        const std::vector<bool> &dirs);
+// window functions over PARTITION BY partition_cols ORDER BY order_cols (docs/semantics.md "Window
+// functions"): t's columns, in t's row order, plus one column per spec
+Status Window(const TablePtr &t, const std::vector<int32_t> &partition_cols, const std::vector<int32_t> &order_cols,
+              const std::vector<bool> &dirs, const std::vector<WindowSpec> &specs, TablePtr &out);
+Status DistributedWindow(const TablePtr &t, const std::vector<int32_t> &partition_cols,
+                         const std::vector<int32_t> &order_cols, const std::vector<bool> &dirs,
+                         const std::vector<WindowSpec> &specs, TablePtr &out);
 Status Shuffle(const TablePtr &t, const std::vector<int> &hash_cols, TablePtr &out);
 Status HashPartition(const TablePtr &t, const std::vector<int> &hash_cols, int num_partitions,
                      std::map<int, TablePtr> *out);
@@ -150,6 +157,9 @@ Status DistributedJoinTables(const std::string &left_id, const std::string &righ
 Status UnionTables(const std::string &a, const std::string &b, const std::string &dest, bool distributed);
 Status SortTable(const std::string &id, int col, const std::string &dest, bool ascending);
 Status TopKTable(const std::string &id, int col, int64_t k, const std::string &dest, bool ascending);
+Status WindowTable(const std::string &id, const std::vector<int32_t> &partition_cols,
+                   const std::vector<int32_t> &order_cols, const std::vector<bool> &dirs,
+                   const std::vector<WindowSpec> &specs, const std::string &dest, bool distributed);
 int64_t RowCount(const std::string &id);
 int32_t ColumnCount(const std::string &id);
 std::vector<std::string> ColumnNames(const std::string &id);

@@ -498,3 +498,41 @@ void batched_copy(const void *const *src, void *const *dst, const int64_t *bytes
    8-byte rows instead of scattered 1-byte runs. */
 void pack_byte_columns(const uint8_t *const *cols, int k, int64_t n, uint64_t *const *words, void *stream);
 void unpack_byte_columns(const uint64_t *const *words, int k, int64_t n, uint8_t *const *cols, void *stream);
+
+/* window.hip (CPU twin cpu_window.cpp): window functions over the sorted positions of a permutation
+   (docs/semantics.md "Window functions").  flags[i]: bit 0 = position i starts a partition, bit 1 =
+   it starts a run of peers (window_flags merges two segment_heads outputs; peer == nullptr: the
+   partition heads; in place is fine).
+   A value scan is three launches over tiles of window_tile_rows() positions:
+     window_tile    gather = true: reads col at perm[i] (raw bits of widths 1/2/4/8, else 0, and the
+                    validity byte) and stores both densely in sorted order (dense_valid == nullptr:
+                    the column has no nulls); gather = false: reads the dense arrays of an earlier
+                    call.  Writes one (flag, aggregate) pair per tile.
+     window_carry   one block; the exclusive segmented scan of the tile pairs = each tile's carry-in,
+                    `step` (<= window_carry_tiles(), <= 0: that) tiles per loop step.  words = int64
+                    words per tile aggregate: 1 for a value scan, 3 for the rank scan (func 5).
+     window_apply   re-scans each tile from the dense values and its carry-in; out[perm[i]] = the
+                    running value (8 bytes for func 0, 1, 4; the column's width for 2, 3),
+                    out_valid[perm[i]] = the value's validity byte when out_valid != nullptr.
+   func: 0 sum of integers (mod 2^64), 1 sum of floats in float64, 2 min, 3 max (both on order_image,
+   written back through order_unimage), 4 count of non-null values.  Null values are skipped.
+   The rank scan needs no column: window_rank_tile / window_carry(words 3, func 5) / window_rank_apply
+   write, where the pointer is not null, ROW_NUMBER, RANK and DENSE_RANK at out[perm[i]] and
+   phead[i] = the sorted position of the head of position i's partition.
+   window_shift: src[perm[i]] = perm[i + delta] when 0 <= i + delta < n lies in i's partition, else -1.
+   The CPU twin is the definition: its window_tile only gathers, its window_carry does nothing, and
+   its apply functions are one sequential loop over all positions. */
+int64_t window_tile_rows();
+int64_t window_carry_tiles();
+void window_flags(const uint8_t *part, const uint8_t *peer, int64_t n, uint8_t *flags, void *stream);
+void window_tile(const ColView &col, const int64_t *perm, const uint8_t *flags, int64_t n, int func, uint64_t *dense,
+                 uint8_t *dense_valid, bool gather, int64_t *tile_agg, uint8_t *tile_flag, void *stream);
+void window_carry(const int64_t *tile_agg, const uint8_t *tile_flag, int64_t ntiles, int words, int func,
+                  int64_t step, int64_t *carry, void *stream);
+void window_apply(const ColView &col, const int64_t *perm, const uint8_t *flags, int64_t n, int func,
+                  const uint64_t *dense, const uint8_t *dense_valid, const int64_t *carry, uint8_t *out,
+                  uint8_t *out_valid, void *stream);
+void window_rank_tile(const uint8_t *flags, int64_t n, int64_t *tile_agg, uint8_t *tile_flag, void *stream);
+void window_rank_apply(const int64_t *perm, const uint8_t *flags, int64_t n, const int64_t *carry,
+                       int64_t *row_number, int64_t *rank, int64_t *dense_rank, int64_t *phead, void *stream);
+void window_shift(const int64_t *perm, const int64_t *phead, int64_t n, int64_t delta, int64_t *src, void *stream);

@@ -31,6 +31,17 @@ CYLON_HD uint64_t order_image(uint64_t bits, int w, int kind) {
   return bits;
 }
 
+// the value bits whose order_image is img (-0.0 comes back as +0.0, every NaN as the quiet NaN)
+CYLON_HD uint64_t order_unimage(uint64_t img, int w, int kind) {
+  const int nb = 8 * w;
+  const uint64_t mask = (nb == 64) ? ~0ull : ((1ull << nb) - 1);
+  const uint64_t sign = 1ull << (nb - 1);
+  img &= mask;
+  if (kind == static_cast<int>(ValueKind::SIGNED_INT)) return img ^ sign;
+  if (kind == static_cast<int>(ValueKind::FLOAT)) return (img & sign) ? (img ^ sign) : (~img & mask);
+  return img;
+}
+
 CYLON_HD bool is_nan_bits(uint64_t bits, int w) {
   if (w == 8) return (bits & 0x7ff0000000000000ull) == 0x7ff0000000000000ull && (bits & 0x000fffffffffffffull);
   if (w == 4) return (bits & 0x7f800000ull) == 0x7f800000ull && (bits & 0x007fffffull);

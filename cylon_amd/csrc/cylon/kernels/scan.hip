@@ -340,6 +340,7 @@ void preload_semi_join();
 void preload_sort();
 void preload_strcast();
 void preload_topk();
+void preload_window();
 
 // Every kernel file's code object, once per process and device (HIP loads a code object on the first
 // launch from it: inside a pipelined join that stalled the host for up to 40 ms while the posted
@@ -366,6 +367,7 @@ void preload_device_code() {
   preload_sort();
   preload_strcast();
   preload_topk();
+  preload_window();
 }
 
 }  // namespace hip

@@ -1,0 +1,255 @@
+// Window functions (docs/semantics.md "Window functions"): t's columns unchanged, in t's row order,
+// plus one column per spec computed along perm = SortIndices(t, partition_cols ++ order_cols).
+//
+// One sort, one flag byte per sorted position (segment_heads over the partition columns and over all
+// key columns, merged by window_flags), then per spec a three-phase segmented scan of
+// kernels/window.hip (window_tile / window_carry / window_apply).  The three ranking functions and the
+// partition heads that LAG / LEAD need come out of one scan of the flags; specs on the same value
+// column share its values gathered into sorted order.  The scans write straight to out[perm[i]], so
+// nothing is sorted back.  The GPU context always takes the kernels: there is no other device path.
+#include <algorithm>
+#include <map>
+#include <set>
+
+#include "../trace.hpp"
+#include "util.hpp"
+
+namespace cylon {
+namespace ops {
+
+namespace {
+
+// kernels/window.hip WinFunc
+constexpr int kSumI = 0, kSumF = 1, kMin = 2, kMax = 3, kCount = 4, kRank = 5;
+
+const char *func_name(WindowFunc f) {
+  switch (f) {
+    case WIN_ROW_NUMBER: return "row_number";
+    case WIN_RANK: return "rank";
+    case WIN_DENSE_RANK: return "dense_rank";
+    case WIN_CUMCOUNT: return "cumcount";
+    case WIN_CUMSUM: return "cumsum";
+    case WIN_CUMMIN: return "cummin";
+    case WIN_CUMMAX: return "cummax";
+    case WIN_LAG: return "lag";
+    case WIN_LEAD: return "lead";
+  }
+  CYLON_THROW(Code::Invalid, "window function " << static_cast<int>(f));
+}
+
+bool is_ranking(WindowFunc f) { return f == WIN_ROW_NUMBER || f == WIN_RANK || f == WIN_DENSE_RANK; }
+bool is_shift(WindowFunc f) { return f == WIN_LAG || f == WIN_LEAD; }
+
+bool scan_value(const Column &c) {
+  if (c.is_var() || !c.type.is_numeric()) return false;
+  const int w = c.type.width();
+  return w == 1 || w == 2 || w == 4 || w == 8;
+}
+
+// the result type of CUMSUM = the group-by's SUM
+Type sum_type(const Column &c) {
+  if (c.type.kind() == ValueKind::FLOAT) return Type::DOUBLE;
+  return c.type.kind() == ValueKind::UNSIGNED_INT ? Type::UINT64 : Type::INT64;
+}
+
+// the kernel function and the output type of a value spec
+std::pair<int, DataType> value_plan(const WindowSpec &s, const Column &c) {
+  switch (s.func) {
+    case WIN_CUMCOUNT: return {kCount, DataType(Type::INT64)};
+    case WIN_CUMSUM: return {c.type.kind() == ValueKind::FLOAT ? kSumF : kSumI, DataType(sum_type(c))};
+    case WIN_CUMMIN: return {kMin, c.type};
+    default: return {kMax, c.type};
+  }
+}
+
+struct Checked {
+  std::vector<bool> asc;           // one per order column
+  std::vector<std::string> names;  // one per spec
+};
+
+Checked check(const TablePtr &t, const std::vector<int> &part, const std::vector<int> &order,
+              const std::vector<bool> &ascending, const std::vector<WindowSpec> &specs) {
+  for (int c : part) CYLON_CHECK(c >= 0 && c < t->Columns(), Code::Invalid, "window partition column " << c);
+  for (int c : order) CYLON_CHECK(c >= 0 && c < t->Columns(), Code::Invalid, "window order column " << c);
+  CYLON_CHECK(part.size() + order.size() <= (size_t)kMaxFusedCols, Code::Invalid,
+              "window: more than " << kMaxFusedCols << " partition and order columns");
+  Checked ck;
+  CYLON_CHECK(ascending.empty() || ascending.size() == 1 || ascending.size() == order.size(), Code::Invalid,
+              "ascending flags must match the order columns");
+  for (size_t i = 0; i < order.size(); ++i)
+    ck.asc.push_back(ascending.empty() ? true : ascending[ascending.size() == 1 ? 0 : i]);
+  std::set<std::string> taken;
+  for (const auto &c : t->columns()) taken.insert(c.name);
+  for (const auto &s : specs) {
+    const char *fn = func_name(s.func);
+    std::string name = s.name;
+    if (is_ranking(s.func)) {
+      if (name.empty()) name = fn;
+    } else {
+      CYLON_CHECK(s.col >= 0 && s.col < t->Columns(), Code::Invalid, "window " << fn << " of column " << s.col);
+      const Column &c = t->column(s.col);
+      if (name.empty()) name = std::string(fn) + "_" + c.name;
+      if (s.func == WIN_CUMSUM || s.func == WIN_CUMMIN || s.func == WIN_CUMMAX)
+        CYLON_CHECK(scan_value(c) && !(s.func == WIN_CUMSUM && c.type.type == Type::HALF_FLOAT), Code::Invalid,
+                    "window " << fn << " needs a fixed-width numeric column, got " << c.type.ToString());
+      if (is_shift(s.func)) CYLON_CHECK(s.arg >= 0, Code::Invalid, "window " << fn << " offset " << s.arg << " < 0");
+    }
+    CYLON_CHECK(taken.insert(name).second, Code::Invalid, "window output column '" << name << "' already exists");
+    ck.names.push_back(name);
+  }
+  return ck;
+}
+
+Column int64_column(const std::string &name, const at::Tensor &v) {
+  return Column(name, DataType(Type::INT64), v.numel(), v);
+}
+
+// the new columns of an empty table
+TablePtr empty_result(const TablePtr &t, const std::vector<WindowSpec> &specs, const Checked &ck) {
+  Exec ex(t->device());
+  std::vector<Column> out = t->columns();
+  for (size_t i = 0; i < specs.size(); ++i) {
+    const WindowSpec &s = specs[i];
+    if (is_ranking(s.func)) {
+      out.push_back(int64_column(ck.names[i], ex.empty_i64(0)));
+    } else if (is_shift(s.func)) {
+      out.push_back(GatherColumn(t->column(s.col), ex.empty_i64(0)).with_name(ck.names[i]));
+    } else {
+      const Column &c = t->column(s.col);
+      out.push_back(make_fixed_column(ck.names[i], value_plan(s, c).second, 0, ex.device,
+                                      s.func != WIN_CUMCOUNT && c.nullable()));
+    }
+  }
+  return Table::Make(t->GetContext(), std::move(out));
+}
+
+int64_t *opt_ptr(const at::Tensor &t) { return t.defined() ? ptr<int64_t>(t) : nullptr; }
+
+struct Dense {  // a value column gathered into sorted order
+  at::Tensor bits, valid;
+};
+
+}  // namespace
+
+TablePtr Window(const TablePtr &t, const std::vector<int> &partition_cols, const std::vector<int> &order_cols,
+                const std::vector<bool> &ascending, const std::vector<WindowSpec> &specs, int64_t carry_step_tiles) {
+  const Checked ck = check(t, partition_cols, order_cols, ascending, specs);
+  if (specs.empty()) return t;
+  const int64_t n = t->Rows();
+  if (n == 0) return empty_result(t, specs, ck);
+  Exec ex(t->device());
+  CYLON_PHASE("window", ex.device);
+  const int64_t max_step = KSIZE(ex, window_carry_tiles);
+  CYLON_CHECK(carry_step_tiles <= max_step, Code::Invalid, "window: carry step of " << carry_step_tiles << " tiles");
+  const int64_t step = carry_step_tiles > 0 ? carry_step_tiles : max_step;
+
+  // the defining order
+  std::vector<int> keys = partition_cols;
+  keys.insert(keys.end(), order_cols.begin(), order_cols.end());
+  std::vector<bool> dirs(partition_cols.size(), true);
+  dirs.insert(dirs.end(), ck.asc.begin(), ck.asc.end());
+  at::Tensor perm = ex.empty_i64(n);
+  if (keys.empty()) {
+    KCALL(ex, iota, ptr<int64_t>(perm), n, 0);
+  } else {
+    perm = SortIndices(t, keys, dirs).contiguous();
+    if (reinterpret_cast<uintptr_t>(perm.data_ptr()) % 16 != 0) perm = perm.clone();  // the scans' 16-byte loads
+  }
+  trace::add_counter("window.sort", keys.empty() ? 0 : 1);
+
+  // bit 0: partition head, bit 1: peer head
+  at::Tensor flags = ex.empty_u8(n), peer;
+  {
+    const std::vector<ColView> pv = views(t, partition_cols);
+    KCALL(ex, segment_heads, pv.data(), (int)pv.size(), ptr<int64_t>(perm), n, ptr<uint8_t>(flags));
+    if (!order_cols.empty()) {
+      const std::vector<ColView> kv = views(t, keys);
+      peer = ex.empty_u8(n);
+      KCALL(ex, segment_heads, kv.data(), (int)kv.size(), ptr<int64_t>(perm), n, ptr<uint8_t>(peer));
+    }
+    KCALL(ex, window_flags, ptr<uint8_t>(flags), peer.defined() ? ptr<uint8_t>(peer) : nullptr, n, ptr<uint8_t>(flags));
+    peer = at::Tensor();
+  }
+
+  const int64_t T = KSIZE(ex, window_tile_rows);
+  const int64_t ntiles = (n + T - 1) / T;
+  int64_t scans = 0;
+
+  // ranking functions and LAG / LEAD: one scan of the flags
+  at::Tensor row_number, rank, dense_rank, phead;
+  for (const auto &s : specs) {
+    if (s.func == WIN_ROW_NUMBER && !row_number.defined()) row_number = ex.empty_i64(n);
+    if (s.func == WIN_RANK && !rank.defined()) rank = ex.empty_i64(n);
+    if (s.func == WIN_DENSE_RANK && !dense_rank.defined()) dense_rank = ex.empty_i64(n);
+    if (is_shift(s.func) && !phead.defined()) phead = ex.empty_i64(n);
+  }
+  if (row_number.defined() || rank.defined() || dense_rank.defined() || phead.defined()) {
+    at::Tensor tagg = ex.empty_i64(3 * ntiles), tflag = ex.empty_u8(ntiles), carry = ex.empty_i64(3 * ntiles);
+    KCALL(ex, window_rank_tile, ptr<uint8_t>(flags), n, ptr<int64_t>(tagg), ptr<uint8_t>(tflag));
+    KCALL(ex, window_carry, ptr<int64_t>(tagg), ptr<uint8_t>(tflag), ntiles, 3, kRank, step, ptr<int64_t>(carry));
+    KCALL(ex, window_rank_apply, ptr<int64_t>(perm), ptr<uint8_t>(flags), n, ptr<int64_t>(carry),
+          opt_ptr(row_number), opt_ptr(rank), opt_ptr(dense_rank), opt_ptr(phead));
+    ++scans;
+  }
+
+  std::map<int, Dense> dense;  // by value column
+  std::vector<Column> out = t->columns();
+  for (size_t i = 0; i < specs.size(); ++i) {
+    const WindowSpec &s = specs[i];
+    const std::string &name = ck.names[i];
+    if (is_ranking(s.func)) {
+      out.push_back(int64_column(name, s.func == WIN_ROW_NUMBER ? row_number : s.func == WIN_RANK ? rank : dense_rank));
+      continue;
+    }
+    const Column &c = t->column(s.col);
+    if (is_shift(s.func)) {
+      const int64_t off = std::min(s.arg, n);  // n rows away is outside every partition
+      at::Tensor src = ex.empty_i64(n);
+      KCALL(ex, window_shift, ptr<int64_t>(perm), ptr<int64_t>(phead), n, s.func == WIN_LAG ? -off : off,
+            ptr<int64_t>(src));
+      out.push_back(GatherColumn(c, src).with_name(name));
+      continue;
+    }
+    const auto plan = value_plan(s, c);
+    const bool nullable_out = s.func != WIN_CUMCOUNT && c.nullable();
+    auto it = dense.find(s.col);
+    const bool gather = it == dense.end();
+    if (gather) {
+      Dense d;
+      d.bits = ex.empty_i64(n);
+      if (c.nullable()) d.valid = ex.empty_u8(n);
+      it = dense.emplace(s.col, d).first;
+    }
+    const Dense &d = it->second;
+    Column col = make_fixed_column(name, plan.second, n, ex.device, nullable_out);
+    at::Tensor tagg = ex.empty_i64(ntiles), tflag = ex.empty_u8(ntiles), carry = ex.empty_i64(ntiles);
+    uint64_t *bits = reinterpret_cast<uint64_t *>(ptr<int64_t>(d.bits));
+    uint8_t *valid = d.valid.defined() ? ptr<uint8_t>(d.valid) : nullptr;
+    const ColView cv = c.view();
+    KCALL(ex, window_tile, cv, ptr<int64_t>(perm), ptr<uint8_t>(flags), n, plan.first, bits, valid, gather,
+          ptr<int64_t>(tagg), ptr<uint8_t>(tflag));
+    KCALL(ex, window_carry, ptr<int64_t>(tagg), ptr<uint8_t>(tflag), ntiles, 1, plan.first, step,
+          ptr<int64_t>(carry));
+    KCALL(ex, window_apply, cv, ptr<int64_t>(perm), ptr<uint8_t>(flags), n, plan.first, bits, valid,
+          ptr<int64_t>(carry), reinterpret_cast<uint8_t *>(col.data.data_ptr()),
+          nullable_out ? col.validity.data_ptr<uint8_t>() : nullptr);
+    ++scans;
+    out.push_back(std::move(col));
+  }
+  trace::add_counter("window.scan", scans);
+  trace::add_counter("window.tiles", scans * ntiles);
+  return Table::Make(t->GetContext(), std::move(out));
+}
+
+TablePtr DistributedWindow(const TablePtr &t, const std::vector<int> &partition_cols,
+                           const std::vector<int> &order_cols, const std::vector<bool> &ascending,
+                           const std::vector<WindowSpec> &specs) {
+  if (t->GetContext()->GetWorldSize() <= 1) return Window(t, partition_cols, order_cols, ascending, specs);
+  CYLON_CHECK(!partition_cols.empty(), Code::Invalid,
+              "a distributed window needs a partition column (a global order is not supported)");
+  check(t, partition_cols, order_cols, ascending, specs);  // every rank fails before the exchange, or none
+  return Window(Shuffle(t, partition_cols), partition_cols, order_cols, ascending, specs);
+}
+
+}  // namespace ops
+}  // namespace cylon

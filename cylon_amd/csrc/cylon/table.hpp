@@ -85,6 +85,27 @@ struct SortOptions {
   static SortOptions Defaults() { return SortOptions(); }
 };
 
+// Window functions (docs/semantics.md "Window functions"), numbered as the C ABI and the bindings
+// pass them.  The frame is always ROWS BETWEEN UNBOUNDED PRECEDING AND CURRENT ROW.
+enum WindowFunc : int {
+  WIN_ROW_NUMBER = 0,
+  WIN_RANK = 1,
+  WIN_DENSE_RANK = 2,
+  WIN_CUMCOUNT = 3,
+  WIN_CUMSUM = 4,
+  WIN_CUMMIN = 5,
+  WIN_CUMMAX = 6,
+  WIN_LAG = 7,
+  WIN_LEAD = 8,
+};
+
+struct WindowSpec {
+  WindowFunc func;
+  int col;           // value column; ignored by the three ranking functions
+  int64_t arg;       // LAG / LEAD: the offset (>= 0)
+  std::string name;  // output column; empty: <func>_<column name>, or the bare ranking function
+};
+
 namespace ops {
 
 // ---- plumbing -------------------------------------------------------------
@@ -184,6 +205,16 @@ TablePtr Sort(const TablePtr &t, const std::vector<int> &cols, const std::vector
 TablePtr TopK(const TablePtr &t, const std::vector<int> &cols, const std::vector<bool> &ascending, int64_t k);
 TablePtr DistributedTopK(const TablePtr &t, const std::vector<int> &cols, const std::vector<bool> &ascending,
                          int64_t k);
+// Window functions (ops/window.cpp): t's columns unchanged, in t's row order, followed by one column
+// per spec, computed over the stable sort by partition_cols (ascending) ++ order_cols (ascending).
+// carry_step_tiles > 0 (tests only) lowers the tiles one step of the carry scan covers.
+// DistributedWindow: shuffle by the partition columns (at least one), then Window on every rank.
+TablePtr Window(const TablePtr &t, const std::vector<int> &partition_cols, const std::vector<int> &order_cols,
+                const std::vector<bool> &ascending, const std::vector<WindowSpec> &specs,
+                int64_t carry_step_tiles = 0);
+TablePtr DistributedWindow(const TablePtr &t, const std::vector<int> &partition_cols,
+                           const std::vector<int> &order_cols, const std::vector<bool> &ascending,
+                           const std::vector<WindowSpec> &specs);
 
 }  // namespace ops
 }  // namespace cylon

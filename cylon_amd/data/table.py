@@ -369,6 +369,55 @@ class Table(PandasOpsMixin):
     def nsmallest(self, n: int, columns) -> "Table":
         return self.topk(n, columns, ascending=True)
 
+    # WindowFunc numbers (csrc/cylon/table.hpp)
+    _WINDOW_FUNCS = {"row_number": 0, "rank": 1, "dense_rank": 2, "cumcount": 3, "cumsum": 4, "cummin": 5,
+                     "cummax": 6, "lag": 7, "lead": 8}
+
+    def _window_args(self, partition_by, order_by, ascending, funcs):
+        part = self._resolve_columns(partition_by) if partition_by is not None else []
+        order = self._resolve_columns(order_by) if order_by is not None else []
+        asc = [bool(a) for a in ascending] if isinstance(ascending, (list, tuple)) else [bool(ascending)] * len(order)
+        if len(asc) != len(order):
+            raise ValueError(f"{len(asc)} ascending flags for {len(order)} order columns")
+        ids, cols, args, names = [], [], [], []
+        for name, spec in (funcs or {}).items():
+            spec = (spec,) if isinstance(spec, str) else tuple(spec)
+            fn = str(spec[0]).lower() if spec else ""
+            if fn not in self._WINDOW_FUNCS:
+                raise ValueError(f"unknown window function {spec[0] if spec else spec!r}; "
+                                 f"one of {sorted(self._WINDOW_FUNCS)}")
+            fid = self._WINDOW_FUNCS[fn]
+            if fid <= 2:
+                if len(spec) != 1:
+                    raise ValueError(f"window function {fn} takes no column")
+                col, arg = -1, 0
+            else:
+                if len(spec) < 2 or len(spec) > (3 if fid >= 7 else 2):
+                    raise ValueError(f"window spec {spec!r}: expected ({fn!r}, column" +
+                                     (", offset)" if fid >= 7 else ")"))
+                col = self._resolve_column(spec[1])
+                arg = int(spec[2]) if len(spec) == 3 else (1 if fid >= 7 else 0)
+            ids.append(fid)
+            cols.append(col)
+            args.append(arg)
+            names.append("" if name is None else str(name))
+        return part, order, asc, ids, cols, args, names
+
+    def window(self, partition_by=None, order_by=None, ascending: Union[bool, List[bool]] = True,
+               funcs: dict = None) -> "Table":
+        """Window functions OVER (PARTITION BY partition_by ORDER BY order_by), frame UNBOUNDED PRECEDING ..
+        CURRENT ROW: this table's columns in its row order plus one column per entry of `funcs`, a dict
+        from output name to "row_number" | "rank" | "dense_rank" | ("cumcount" | "cumsum" | "cummin" |
+        "cummax", column) | ("lag" | "lead", column[, offset = 1]).  Ties keep row order; NaN sorts
+        after every number and null after NaN in both directions (docs/semantics.md "Window functions")."""
+        return self._wrap(C.window(self._t, *self._window_args(partition_by, order_by, ascending, funcs)))
+
+    def distributed_window(self, partition_by=None, order_by=None, ascending: Union[bool, List[bool]] = True,
+                           funcs: dict = None) -> "Table":
+        """window() after a shuffle by the partition columns (at least one when the world is larger than
+        1); the output row order is unspecified."""
+        return self._wrap(C.distributed_window(self._t, *self._window_args(partition_by, order_by, ascending, funcs)))
+
     def shuffle(self, hash_columns: List = None) -> "Table":
         return self._wrap(C.shuffle(self._t, self._resolve_columns(hash_columns)))
 

@@ -402,6 +402,15 @@ class DataFrame(object):
     def nsmallest(self, n: int, columns, keep: str = "first", env: CylonEnv = None) -> "DataFrame":
         return self._n_extreme(n, columns, keep, False, env)
 
+    def window(self, partition_by=None, order_by=None, ascending: Union[bool, List[bool]] = True, funcs: dict = None,
+               env: CylonEnv = None) -> "DataFrame":
+        """Window functions (Table.window): ranking, running aggregates and lag / lead per partition, e.g.
+        funcs={"rn": "row_number", "bal": ("cumsum", "amount"), "prev": ("lag", "amount", 1)}.  With an env
+        of more than one rank the rows are first shuffled by the partition columns."""
+        if env is None or env.world_size <= 1:
+            return DataFrame(self._table.window(partition_by, order_by, ascending, funcs))
+        return DataFrame(self._change_context(env)._table.distributed_window(partition_by, order_by, ascending, funcs))
+
     def groupby(self, by, agg: dict, algorithm: str = "hash", env: CylonEnv = None) -> "DataFrame":
         if env is None:
             return DataFrame(self._table.local_groupby(by, agg, algorithm))

@@ -48,6 +48,16 @@ int cylon_set_op(const char *a_id, const char *b_id, int op, int distributed, co
 int cylon_sort(const char *table_id, int column, int ascending, const char *dest_id);
 /* ORDER BY column LIMIT k: the first min(k, rows) rows of the stable sort; k < 0 is an error */
 int cylon_topk(const char *table_id, int column, int ascending, int64_t k, const char *dest_id);
+/* window functions over PARTITION BY partition_columns ORDER BY order_columns (ascending[i] != 0:
+   ascending; NULL: all ascending); the frame is UNBOUNDED PRECEDING .. CURRENT ROW.  Spec i:
+   funcs[i] = 0 ROW_NUMBER, 1 RANK, 2 DENSE_RANK, 3 CUMCOUNT, 4 CUMSUM, 5 CUMMIN, 6 CUMMAX, 7 LAG,
+   8 LEAD; spec_columns[i] its value column (ignored by 0..2), spec_args[i] the LAG / LEAD offset,
+   names[i] the output column (NULL or "": the default name).  The result holds the table's columns
+   in its row order, then one column per spec.  distributed != 0 needs a partition column. */
+int cylon_window(const char *table_id, const int32_t *partition_columns, int npartition,
+                 const int32_t *order_columns, const int32_t *ascending, int norder, const int32_t *funcs,
+                 const int32_t *spec_columns, const int64_t *spec_args, const char *const *names, int nspecs,
+                 int distributed, const char *dest_id);
 int cylon_project(const char *table_id, const int32_t *columns, int ncolumns, const char *dest_id);
 
 int cylon_merge(const char *const *table_ids, int ntables, const char *dest_id);

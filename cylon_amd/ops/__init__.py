@@ -59,6 +59,16 @@ def distributed_topk(t: Table, k: int, order_by=None, ascending: Union[bool, Lis
     return t.distributed_topk(k, order_by, ascending)
 
 
+def window(t: Table, partition_by=None, order_by=None, ascending: Union[bool, List[bool]] = True,
+           funcs: dict = None) -> Table:
+    return t.window(partition_by, order_by, ascending, funcs)
+
+
+def distributed_window(t: Table, partition_by=None, order_by=None, ascending: Union[bool, List[bool]] = True,
+                       funcs: dict = None) -> Table:
+    return t.distributed_window(partition_by, order_by, ascending, funcs)
+
+
 def shuffle(t: Table, hash_columns: List = None) -> Table:
     return t.shuffle(hash_columns)
 
@@ -94,5 +104,5 @@ def merge(tables: Sequence[Table]) -> Table:
 
 __all__ = ["join", "distributed_join", "union", "subtract", "intersect", "distributed_union",
            "distributed_subtract", "distributed_intersect", "sort", "distributed_sort", "topk",
-           "distributed_topk", "shuffle",
+           "distributed_topk", "window", "distributed_window", "shuffle",
            "hash_partition", "unique", "distributed_unique", "groupby", "local_groupby", "project", "merge"]

@@ -52,7 +52,7 @@ int main(int argc, char **argv) {
     return p;
   };
 
-  TablePtr a, b, j, js, u, i, s, q, srt, top, g, sum, back;
+  TablePtr a, b, j, js, u, i, s, q, srt, top, win, g, sum, back;
   CHECK_OK(cylon::FromCSV(ctx, path(argv[2]), a));
   CHECK_OK(cylon::FromCSV(ctx, path(argv[3]), b, cylon::io::CSVReadOptions().WithDelimiter(',').UseThreads(true).BlockSize(1 << 20)));
   report("left", a);
@@ -76,6 +76,10 @@ int main(int argc, char **argv) {
   report("sort", srt);
   CHECK_OK(cylon::TopK(a, {0}, 5, top, {false}));  // ORDER BY column 0 DESC LIMIT 5
   report("topk", top);
+  // ROW_NUMBER() and SUM(column 1) OVER (PARTITION BY column 0 ORDER BY column 1)
+  CHECK_OK(cylon::Window(a, {0}, {1}, {true},
+                         {{cylon::WIN_ROW_NUMBER, -1, 0, "rn"}, {cylon::WIN_CUMSUM, 1, 0, "running"}}, win));
+  report("window", win);
   CHECK_OK(cylon::DistributedHashGroupBy(a, {0}, {1}, {cylon::AGG_SUM}, g));
   report("groupby_sum", g);
   CHECK_OK(cylon::compute::Sum(a, 1, sum));
