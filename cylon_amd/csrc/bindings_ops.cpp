@@ -324,10 +324,56 @@ void register_extended_ops(py::module &m) {
       },
       py::arg("table"), py::arg("partition_cols"), py::arg("order_cols"), py::arg("ascending"), py::arg("funcs"),
       py::arg("cols"), py::arg("args"), py::arg("names"), rel);
+  // the same with a frame per spec (ROLLING functions: rows before and after the current one, >= the
+  // table's rows meaning unbounded, and min_periods); accepts every WindowFunc
+  auto frame_specs = [](const std::vector<int> &funcs, const std::vector<int> &cols, const std::vector<int64_t> &args,
+                        const std::vector<std::string> &names, const std::vector<int64_t> &preceding,
+                        const std::vector<int64_t> &following, const std::vector<int64_t> &min_periods) {
+    const size_t k = funcs.size();
+    CYLON_CHECK(cols.size() == k && args.size() == k && names.size() == k && preceding.size() == k &&
+                    following.size() == k && min_periods.size() == k,
+                Code::Invalid, "window spec lists differ in length");
+    std::vector<WindowSpec> specs;
+    for (size_t i = 0; i < k; ++i) {
+      CYLON_CHECK(funcs[i] >= WIN_ROW_NUMBER && funcs[i] <= WIN_ROLLING_MAX, Code::Invalid,
+                  "window function " << funcs[i]);
+      specs.push_back({static_cast<WindowFunc>(funcs[i]), cols[i], args[i], names[i], preceding[i], following[i],
+                       min_periods[i]});
+    }
+    return specs;
+  };
+  m.def(
+      "window_frames",
+      [frame_specs](const TablePtr &t, const std::vector<int> &part, const std::vector<int> &order,
+                    const std::vector<bool> &asc, const std::vector<int> &funcs, const std::vector<int> &cols,
+                    const std::vector<int64_t> &args, const std::vector<std::string> &names,
+                    const std::vector<int64_t> &preceding, const std::vector<int64_t> &following,
+                    const std::vector<int64_t> &min_periods, int64_t carry_step_tiles) {
+        return ops::Window(t, part, order, asc, frame_specs(funcs, cols, args, names, preceding, following, min_periods),
+                           carry_step_tiles);
+      },
+      py::arg("table"), py::arg("partition_cols"), py::arg("order_cols"), py::arg("ascending"), py::arg("funcs"),
+      py::arg("cols"), py::arg("args"), py::arg("names"), py::arg("preceding"), py::arg("following"),
+      py::arg("min_periods"), py::arg("carry_step_tiles") = 0, rel);
+  m.def(
+      "distributed_window_frames",
+      [frame_specs](const TablePtr &t, const std::vector<int> &part, const std::vector<int> &order,
+                    const std::vector<bool> &asc, const std::vector<int> &funcs, const std::vector<int> &cols,
+                    const std::vector<int64_t> &args, const std::vector<std::string> &names,
+                    const std::vector<int64_t> &preceding, const std::vector<int64_t> &following,
+                    const std::vector<int64_t> &min_periods) {
+        return ops::DistributedWindow(t, part, order, asc,
+                                      frame_specs(funcs, cols, args, names, preceding, following, min_periods));
+      },
+      py::arg("table"), py::arg("partition_cols"), py::arg("order_cols"), py::arg("ascending"), py::arg("funcs"),
+      py::arg("cols"), py::arg("args"), py::arg("names"), py::arg("preceding"), py::arg("following"),
+      py::arg("min_periods"), rel);
   // rows per tile of the window scans and tiles per step of their carry scan (kernels/window.hip); the
   // CPU twin is one sequential loop and reports the same numbers
   m.def("window_tile_rows", []() { return hip::window_tile_rows(); });
   m.def("window_carry_tiles", []() { return hip::window_carry_tiles(); });
+  // the widest frame (preceding + following + 1) that the one-launch LDS kernel of kernels/rolling.hip takes
+  m.def("window_frame_lds_rows", []() { return hip::window_frame_lds_rows(); });
   // ---- streaming op graph (C24) ------------------------------------------
   m.def(
       "dis_join_op",

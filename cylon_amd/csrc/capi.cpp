@@ -185,6 +185,28 @@ CYLON_CAPI int cylon_window(const char *id, const int32_t *partition_cols, int n
   });
 }
 
+CYLON_CAPI int cylon_window_frames(const char *id, const int32_t *partition_cols, int npartition,
+                                   const int32_t *order_cols, const int32_t *ascending, int norder,
+                                   const int32_t *funcs, const int32_t *spec_cols, const int64_t *spec_args,
+                                   const int64_t *preceding, const int64_t *following, const int64_t *min_periods,
+                                   const char *const *names, int nspecs, int distributed, const char *dest) {
+  return guard([&] {
+    std::vector<bool> dirs;
+    for (int i = 0; i < norder; ++i) dirs.push_back(ascending == nullptr || ascending[i] != 0);
+    std::vector<WindowSpec> specs;
+    for (int i = 0; i < nspecs; ++i) {
+      if (funcs[i] < WIN_ROW_NUMBER || funcs[i] > WIN_ROLLING_MAX)
+        return status(Status(Code::Invalid, "window function " + std::to_string(funcs[i])));
+      specs.push_back({static_cast<WindowFunc>(funcs[i]), spec_cols ? spec_cols[i] : -1, spec_args ? spec_args[i] : 0,
+                       names && names[i] ? names[i] : "", preceding ? preceding[i] : 0, following ? following[i] : 0,
+                       min_periods ? min_periods[i] : 1});
+    }
+    return status(WindowTable(id, std::vector<int32_t>(partition_cols, partition_cols + npartition),
+                              std::vector<int32_t>(order_cols, order_cols + norder), dirs, specs, dest,
+                              distributed != 0));
+  });
+}
+
 CYLON_CAPI int cylon_project(const char *id, const int32_t *cols, int n, const char *dest) {
   return guard([&] {
     TablePtr out;

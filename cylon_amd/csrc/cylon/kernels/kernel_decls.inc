@@ -536,3 +536,36 @@ void window_rank_tile(const uint8_t *flags, int64_t n, int64_t *tile_agg, uint8_
 void window_rank_apply(const int64_t *perm, const uint8_t *flags, int64_t n, const int64_t *carry,
                        int64_t *row_number, int64_t *rank, int64_t *dense_rank, int64_t *phead, void *stream);
 void window_shift(const int64_t *perm, const int64_t *phead, int64_t n, int64_t delta, int64_t *src, void *stream);
+
+/* rolling.hip (CPU twin cpu_rolling.cpp): aggregates over the frame [max(i - preceding, head),
+   min(i + following, tail)] of sorted position i (docs/semantics.md "Framed aggregates"), from the dense
+   values of window_tile, the flags, phead, and rtail = the phead of the rank scan run over
+   window_rev_flags' output (rflags[k] = 3 where sorted position n - 1 - k ends a partition, else 0;
+   the tail of position i is n - 1 - rtail[n - 1 - i]).  func as window_apply's (0 .. 4); mean: func
+   0 / 1 divided by the frame's non-null count m, as float64.  out[perm[i]] = the result (8 bytes, or
+   the column's width for func 2, 3), out_valid[perm[i]] = (m >= min_periods) when not nullptr.
+   n < 2^32, 0 <= preceding, following <= n.
+     rolling_lds      preceding + following + 1 <= window_frame_lds_rows(): one launch.
+     rolling_tile / window_carry (twice: the aggregates with func, the counts with func 4, one tile
+     flag array) / rolling_scan: the scan that restarts at partition edges and at the edges of the
+                      blocks of w = preceding + following + 1 positions, forwards (restarts = flags) or,
+                      reverse = true, over the reversed order (restarts = rflags); scan[k], scan_cnt[k]
+                      are in scan order.
+     rolling_combine  the results from the forward and the reversed scan.
+   The CPU twin is sequential: its rolling_tile does nothing. */
+int64_t window_frame_lds_rows();
+void window_rev_flags(const uint8_t *flags, int64_t n, uint8_t *rflags, void *stream);
+void rolling_lds(const ColView &col, const int64_t *perm, const uint8_t *flags, const int64_t *phead,
+                 const int64_t *rtail, int64_t n, int func, bool mean, int64_t preceding, int64_t following,
+                 int64_t min_periods, const uint64_t *dense, const uint8_t *dense_valid, uint8_t *out,
+                 uint8_t *out_valid, void *stream);
+void rolling_tile(const ColView &col, const uint8_t *restarts, int64_t n, int func, int64_t w, bool reverse,
+                  const uint64_t *dense, const uint8_t *dense_valid, int64_t *tile_agg, int64_t *tile_cnt,
+                  uint8_t *tile_flag, void *stream);
+void rolling_scan(const ColView &col, const uint8_t *restarts, int64_t n, int func, int64_t w, bool reverse,
+                  const uint64_t *dense, const uint8_t *dense_valid, const int64_t *carry, const int64_t *carry_cnt,
+                  uint64_t *scan, uint32_t *scan_cnt, void *stream);
+void rolling_combine(const ColView &col, const int64_t *perm, const int64_t *phead, const int64_t *rtail, int64_t n,
+                     int func, bool mean, int64_t preceding, int64_t following, int64_t min_periods,
+                     const uint64_t *fwd, const uint32_t *fwd_cnt, const uint64_t *bwd, const uint32_t *bwd_cnt,
+                     uint8_t *out, uint8_t *out_valid, void *stream);

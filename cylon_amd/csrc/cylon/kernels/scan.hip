@@ -334,6 +334,7 @@ void preload_radix_join();
 void preload_radix_setops();
 void preload_range();
 void preload_range_join();
+void preload_rolling();
 void preload_seg_sort();
 void preload_select();
 void preload_semi_join();
@@ -360,6 +361,7 @@ void preload_device_code() {
   preload_radix_setops();
   preload_range();
   preload_range_join();
+  preload_rolling();
   preload_scan();
   preload_seg_sort();
   preload_select();

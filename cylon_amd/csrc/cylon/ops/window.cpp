@@ -7,6 +7,12 @@
 // partition heads that LAG / LEAD need come out of one scan of the flags; specs on the same value
 // column share its values gathered into sorted order.  The scans write straight to out[perm[i]], so
 // nothing is sorted back.  The GPU context always takes the kernels: there is no other device path.
+//
+// A ROLLING spec (a bounded ROWS frame) shares the sort, the flags, the gathered values and the
+// partition heads; the partition tails come from the same rank scan run over the reversed flags.  A
+// frame of at most window_frame_lds_rows() rows is one launch of kernels/rolling.hip (rolling_lds);
+// a wider one scans forwards and over the reversed order (rolling_tile / window_carry /
+// rolling_scan) and combines the two (rolling_combine).
 #include <algorithm>
 #include <map>
 #include <set>
@@ -33,12 +39,18 @@ const char *func_name(WindowFunc f) {
     case WIN_CUMMAX: return "cummax";
     case WIN_LAG: return "lag";
     case WIN_LEAD: return "lead";
+    case WIN_ROLLING_COUNT: return "rolling_count";
+    case WIN_ROLLING_SUM: return "rolling_sum";
+    case WIN_ROLLING_MEAN: return "rolling_mean";
+    case WIN_ROLLING_MIN: return "rolling_min";
+    case WIN_ROLLING_MAX: return "rolling_max";
   }
   CYLON_THROW(Code::Invalid, "window function " << static_cast<int>(f));
 }
 
 bool is_ranking(WindowFunc f) { return f == WIN_ROW_NUMBER || f == WIN_RANK || f == WIN_DENSE_RANK; }
 bool is_shift(WindowFunc f) { return f == WIN_LAG || f == WIN_LEAD; }
+bool is_rolling(WindowFunc f) { return f >= WIN_ROLLING_COUNT && f <= WIN_ROLLING_MAX; }
 
 bool scan_value(const Column &c) {
   if (c.is_var() || !c.type.is_numeric()) return false;
@@ -55,8 +67,12 @@ Type sum_type(const Column &c) {
 // the kernel function and the output type of a value spec
 std::pair<int, DataType> value_plan(const WindowSpec &s, const Column &c) {
   switch (s.func) {
-    case WIN_CUMCOUNT: return {kCount, DataType(Type::INT64)};
+    case WIN_CUMCOUNT:
+    case WIN_ROLLING_COUNT: return {kCount, DataType(Type::INT64)};
+    case WIN_ROLLING_MEAN: return {c.type.kind() == ValueKind::FLOAT ? kSumF : kSumI, DataType(Type::DOUBLE)};
+    case WIN_ROLLING_SUM:
     case WIN_CUMSUM: return {c.type.kind() == ValueKind::FLOAT ? kSumF : kSumI, DataType(sum_type(c))};
+    case WIN_ROLLING_MIN:
     case WIN_CUMMIN: return {kMin, c.type};
     default: return {kMax, c.type};
   }
@@ -93,6 +109,17 @@ Checked check(const TablePtr &t, const std::vector<int> &part, const std::vector
         CYLON_CHECK(scan_value(c) && !(s.func == WIN_CUMSUM && c.type.type == Type::HALF_FLOAT), Code::Invalid,
                     "window " << fn << " needs a fixed-width numeric column, got " << c.type.ToString());
       if (is_shift(s.func)) CYLON_CHECK(s.arg >= 0, Code::Invalid, "window " << fn << " offset " << s.arg << " < 0");
+      if (is_rolling(s.func)) {
+        CYLON_CHECK(t->Rows() < (int64_t(1) << 32), Code::Invalid,
+                    "window " << fn << " over " << t->Rows() << " rows: framed functions take fewer than 2^32");
+        const bool sum = s.func == WIN_ROLLING_SUM || s.func == WIN_ROLLING_MEAN;
+        CYLON_CHECK(s.func == WIN_ROLLING_COUNT || (scan_value(c) && !(sum && c.type.type == Type::HALF_FLOAT)),
+                    Code::Invalid, "window " << fn << " needs a fixed-width numeric column, got " << c.type.ToString());
+        CYLON_CHECK(s.preceding >= 0 && s.following >= 0, Code::Invalid,
+                    "window " << fn << " frame of " << s.preceding << " preceding, " << s.following << " following");
+        CYLON_CHECK(s.func == WIN_ROLLING_COUNT || s.min_periods >= 1, Code::Invalid,
+                    "window " << fn << " min_periods " << s.min_periods << " < 1");
+      }
     }
     CYLON_CHECK(taken.insert(name).second, Code::Invalid, "window output column '" << name << "' already exists");
     ck.names.push_back(name);
@@ -102,6 +129,13 @@ Checked check(const TablePtr &t, const std::vector<int> &part, const std::vector
 
 Column int64_column(const std::string &name, const at::Tensor &v) {
   return Column(name, DataType(Type::INT64), v.numel(), v);
+}
+
+// A running aggregate is null where its row's value is; a framed one where the frame holds fewer than
+// min_periods values, which a frame of a column without nulls can only do for min_periods > 1.
+bool nullable_result(const WindowSpec &s, const Column &c) {
+  if (s.func == WIN_CUMCOUNT || s.func == WIN_ROLLING_COUNT) return false;
+  return c.nullable() || (is_rolling(s.func) && s.min_periods > 1);
 }
 
 // the new columns of an empty table
@@ -116,8 +150,7 @@ TablePtr empty_result(const TablePtr &t, const std::vector<WindowSpec> &specs, c
       out.push_back(GatherColumn(t->column(s.col), ex.empty_i64(0)).with_name(ck.names[i]));
     } else {
       const Column &c = t->column(s.col);
-      out.push_back(make_fixed_column(ck.names[i], value_plan(s, c).second, 0, ex.device,
-                                      s.func != WIN_CUMCOUNT && c.nullable()));
+      out.push_back(make_fixed_column(ck.names[i], value_plan(s, c).second, 0, ex.device, nullable_result(s, c)));
     }
   }
   return Table::Make(t->GetContext(), std::move(out));
@@ -177,11 +210,13 @@ TablePtr Window(const TablePtr &t, const std::vector<int> &partition_cols, const
 
   // ranking functions and LAG / LEAD: one scan of the flags
   at::Tensor row_number, rank, dense_rank, phead;
+  bool framed = false;
   for (const auto &s : specs) {
     if (s.func == WIN_ROW_NUMBER && !row_number.defined()) row_number = ex.empty_i64(n);
     if (s.func == WIN_RANK && !rank.defined()) rank = ex.empty_i64(n);
     if (s.func == WIN_DENSE_RANK && !dense_rank.defined()) dense_rank = ex.empty_i64(n);
-    if (is_shift(s.func) && !phead.defined()) phead = ex.empty_i64(n);
+    if ((is_shift(s.func) || is_rolling(s.func)) && !phead.defined()) phead = ex.empty_i64(n);
+    if (is_rolling(s.func)) framed = true;
   }
   if (row_number.defined() || rank.defined() || dense_rank.defined() || phead.defined()) {
     at::Tensor tagg = ex.empty_i64(3 * ntiles), tflag = ex.empty_u8(ntiles), carry = ex.empty_i64(3 * ntiles);
@@ -191,6 +226,22 @@ TablePtr Window(const TablePtr &t, const std::vector<int> &partition_cols, const
           opt_ptr(row_number), opt_ptr(rank), opt_ptr(dense_rank), opt_ptr(phead));
     ++scans;
   }
+
+  // framed specs: the partition tails, as the heads of the reversed order
+  at::Tensor rflags, rtail;
+  if (framed) {
+    rflags = ex.empty_u8(n);
+    rtail = ex.empty_i64(n);
+    at::Tensor tagg = ex.empty_i64(3 * ntiles), tflag = ex.empty_u8(ntiles), carry = ex.empty_i64(3 * ntiles);
+    KCALL(ex, window_rev_flags, ptr<uint8_t>(flags), n, ptr<uint8_t>(rflags));
+    KCALL(ex, window_rank_tile, ptr<uint8_t>(rflags), n, ptr<int64_t>(tagg), ptr<uint8_t>(tflag));
+    KCALL(ex, window_carry, ptr<int64_t>(tagg), ptr<uint8_t>(tflag), ntiles, 3, kRank, step, ptr<int64_t>(carry));
+    KCALL(ex, window_rank_apply, ptr<int64_t>(perm), ptr<uint8_t>(rflags), n, ptr<int64_t>(carry), nullptr, nullptr,
+          nullptr, ptr<int64_t>(rtail));
+    ++scans;
+  }
+  const int64_t lds_rows = KSIZE(ex, window_frame_lds_rows);
+  int64_t frames_lds = 0, frames_wide = 0;
 
   std::map<int, Dense> dense;  // by value column
   std::vector<Column> out = t->columns();
@@ -211,7 +262,7 @@ TablePtr Window(const TablePtr &t, const std::vector<int> &partition_cols, const
       continue;
     }
     const auto plan = value_plan(s, c);
-    const bool nullable_out = s.func != WIN_CUMCOUNT && c.nullable();
+    const bool nullable_out = nullable_result(s, c);
     auto it = dense.find(s.col);
     const bool gather = it == dense.end();
     if (gather) {
@@ -226,6 +277,47 @@ TablePtr Window(const TablePtr &t, const std::vector<int> &partition_cols, const
     uint64_t *bits = reinterpret_cast<uint64_t *>(ptr<int64_t>(d.bits));
     uint8_t *valid = d.valid.defined() ? ptr<uint8_t>(d.valid) : nullptr;
     const ColView cv = c.view();
+    if (is_rolling(s.func)) {
+      // the dense values first (window_tile's tile pairs are not used: COUNT suits every column)
+      if (gather)
+        KCALL(ex, window_tile, cv, ptr<int64_t>(perm), ptr<uint8_t>(flags), n, kCount, bits, valid, true,
+              ptr<int64_t>(tagg), ptr<uint8_t>(tflag));
+      const int64_t pre = std::min(s.preceding, n), fol = std::min(s.following, n);  // n rows: unbounded
+      const int64_t w = pre + fol + 1;
+      const bool mean = s.func == WIN_ROLLING_MEAN;
+      const int64_t minp = s.func == WIN_ROLLING_COUNT ? 0 : s.min_periods;  // COUNT ignores it
+      uint8_t *o = reinterpret_cast<uint8_t *>(col.data.data_ptr());
+      uint8_t *ov = nullable_out ? col.validity.data_ptr<uint8_t>() : nullptr;
+      if (w <= lds_rows) {
+        KCALL(ex, rolling_lds, cv, ptr<int64_t>(perm), ptr<uint8_t>(flags), ptr<int64_t>(phead), ptr<int64_t>(rtail), n,
+              plan.first, mean, pre, fol, minp, bits, valid, o, ov);
+        ++frames_lds;
+      } else {
+        at::Tensor scan[2] = {ex.empty_i64(n), ex.empty_i64(n)};
+        at::Tensor cnt[2] = {ex.empty_i64((n + 1) / 2), ex.empty_i64((n + 1) / 2)};  // n uint32
+        at::Tensor tcnt = ex.empty_i64(ntiles), ccnt = ex.empty_i64(ntiles);
+        for (int rev = 0; rev < 2; ++rev) {
+          const uint8_t *restarts = rev ? ptr<uint8_t>(rflags) : ptr<uint8_t>(flags);
+          KCALL(ex, rolling_tile, cv, restarts, n, plan.first, w, rev != 0, bits, valid, ptr<int64_t>(tagg),
+                ptr<int64_t>(tcnt), ptr<uint8_t>(tflag));
+          KCALL(ex, window_carry, ptr<int64_t>(tagg), ptr<uint8_t>(tflag), ntiles, 1, plan.first, step,
+                ptr<int64_t>(carry));
+          KCALL(ex, window_carry, ptr<int64_t>(tcnt), ptr<uint8_t>(tflag), ntiles, 1, kCount, step,
+                ptr<int64_t>(ccnt));
+          KCALL(ex, rolling_scan, cv, restarts, n, plan.first, w, rev != 0, bits, valid, ptr<int64_t>(carry),
+                ptr<int64_t>(ccnt), reinterpret_cast<uint64_t *>(ptr<int64_t>(scan[rev])),
+                reinterpret_cast<uint32_t *>(ptr<int64_t>(cnt[rev])));
+        }
+        KCALL(ex, rolling_combine, cv, ptr<int64_t>(perm), ptr<int64_t>(phead), ptr<int64_t>(rtail), n, plan.first, mean,
+              pre, fol, minp, reinterpret_cast<uint64_t *>(ptr<int64_t>(scan[0])),
+              reinterpret_cast<uint32_t *>(ptr<int64_t>(cnt[0])), reinterpret_cast<uint64_t *>(ptr<int64_t>(scan[1])),
+              reinterpret_cast<uint32_t *>(ptr<int64_t>(cnt[1])), o, ov);
+        ++frames_wide;
+      }
+      ++scans;
+      out.push_back(std::move(col));
+      continue;
+    }
     KCALL(ex, window_tile, cv, ptr<int64_t>(perm), ptr<uint8_t>(flags), n, plan.first, bits, valid, gather,
           ptr<int64_t>(tagg), ptr<uint8_t>(tflag));
     KCALL(ex, window_carry, ptr<int64_t>(tagg), ptr<uint8_t>(tflag), ntiles, 1, plan.first, step,
@@ -238,6 +330,8 @@ TablePtr Window(const TablePtr &t, const std::vector<int> &partition_cols, const
   }
   trace::add_counter("window.scan", scans);
   trace::add_counter("window.tiles", scans * ntiles);
+  if (frames_lds) trace::add_counter("window.frame.lds", frames_lds);
+  if (frames_wide) trace::add_counter("window.frame.wide", frames_wide);
   return Table::Make(t->GetContext(), std::move(out));
 }
 

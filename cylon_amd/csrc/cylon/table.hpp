@@ -86,7 +86,8 @@ struct SortOptions {
 };
 
 // Window functions (docs/semantics.md "Window functions"), numbered as the C ABI and the bindings
-// pass them.  The frame is always ROWS BETWEEN UNBOUNDED PRECEDING AND CURRENT ROW.
+// pass them.  Functions 0 .. 8 have the frame ROWS BETWEEN UNBOUNDED PRECEDING AND CURRENT ROW; the
+// ROLLING functions have ROWS BETWEEN preceding PRECEDING AND following FOLLOWING.
 enum WindowFunc : int {
   WIN_ROW_NUMBER = 0,
   WIN_RANK = 1,
@@ -97,6 +98,11 @@ enum WindowFunc : int {
   WIN_CUMMAX = 6,
   WIN_LAG = 7,
   WIN_LEAD = 8,
+  WIN_ROLLING_COUNT = 9,
+  WIN_ROLLING_SUM = 10,
+  WIN_ROLLING_MEAN = 11,
+  WIN_ROLLING_MIN = 12,
+  WIN_ROLLING_MAX = 13,
 };
 
 struct WindowSpec {
@@ -104,6 +110,11 @@ struct WindowSpec {
   int col;           // value column; ignored by the three ranking functions
   int64_t arg;       // LAG / LEAD: the offset (>= 0)
   std::string name;  // output column; empty: <func>_<column name>, or the bare ranking function
+  // ROLLING functions: rows of the partition before and after the current one (>= 0; >= the table's
+  // rows: unbounded), and the non-null values below which the result is null (>= 1)
+  int64_t preceding = 0;
+  int64_t following = 0;
+  int64_t min_periods = 1;
 };
 
 namespace ops {

@@ -372,36 +372,75 @@ class Table(PandasOpsMixin):
     # WindowFunc numbers (csrc/cylon/table.hpp)
     _WINDOW_FUNCS = {"row_number": 0, "rank": 1, "dense_rank": 2, "cumcount": 3, "cumsum": 4, "cummin": 5,
                      "cummax": 6, "lag": 7, "lead": 8}
+    # framed functions: they go through C.window_frames, which C.window's numbering stops short of
+    _ROLLING_FUNCS = {"rolling_count": 9, "rolling_sum": 10, "rolling_mean": 11, "rolling_min": 12,
+                      "rolling_max": 13}
+    _UNBOUNDED = (1 << 63) - 1
 
-    def _window_args(self, partition_by, order_by, ascending, funcs):
+    @classmethod
+    def _is_rolling(cls, spec):
+        return (not isinstance(spec, str) and len(spec) > 0 and isinstance(spec[0], str)
+                and spec[0].lower() in cls._ROLLING_FUNCS)
+
+    def _window_keys(self, partition_by, order_by, ascending):
         part = self._resolve_columns(partition_by) if partition_by is not None else []
         order = self._resolve_columns(order_by) if order_by is not None else []
         asc = [bool(a) for a in ascending] if isinstance(ascending, (list, tuple)) else [bool(ascending)] * len(order)
         if len(asc) != len(order):
             raise ValueError(f"{len(asc)} ascending flags for {len(order)} order columns")
+        return part, order, asc
+
+    def _window_spec(self, spec):
+        """(WindowFunc number, value column, LAG / LEAD offset) of a spec without a frame"""
+        spec = (spec,) if isinstance(spec, str) else tuple(spec)
+        fn = str(spec[0]).lower() if spec else ""
+        if fn not in self._WINDOW_FUNCS:
+            raise ValueError(f"unknown window function {spec[0] if spec else spec!r}; "
+                             f"one of {sorted(self._WINDOW_FUNCS)}")
+        fid = self._WINDOW_FUNCS[fn]
+        if fid <= 2:
+            if len(spec) != 1:
+                raise ValueError(f"window function {fn} takes no column")
+            return fid, -1, 0
+        if len(spec) < 2 or len(spec) > (3 if fid >= 7 else 2):
+            raise ValueError(f"window spec {spec!r}: expected ({fn!r}, column" + (", offset)" if fid >= 7 else ")"))
+        return fid, self._resolve_column(spec[1]), int(spec[2]) if len(spec) == 3 else (1 if fid >= 7 else 0)
+
+    def _rolling_spec(self, spec):
+        """(WindowFunc number, value column, preceding, following, min_periods) of a rolling spec"""
+        spec = tuple(spec)
+        fn = spec[0].lower()
+        if len(spec) < 4 or len(spec) > 5:
+            raise ValueError(f"window spec {spec!r}: expected ({fn!r}, column, preceding, following[, min_periods])")
+        pre, fol = (self._UNBOUNDED if b is None else int(b) for b in spec[2:4])
+        return (self._ROLLING_FUNCS[fn], self._resolve_column(spec[1]), pre, fol,
+                int(spec[4]) if len(spec) == 5 else 1)
+
+    def _window_args(self, partition_by, order_by, ascending, funcs):
+        part, order, asc = self._window_keys(partition_by, order_by, ascending)
         ids, cols, args, names = [], [], [], []
         for name, spec in (funcs or {}).items():
-            spec = (spec,) if isinstance(spec, str) else tuple(spec)
-            fn = str(spec[0]).lower() if spec else ""
-            if fn not in self._WINDOW_FUNCS:
-                raise ValueError(f"unknown window function {spec[0] if spec else spec!r}; "
-                                 f"one of {sorted(self._WINDOW_FUNCS)}")
-            fid = self._WINDOW_FUNCS[fn]
-            if fid <= 2:
-                if len(spec) != 1:
-                    raise ValueError(f"window function {fn} takes no column")
-                col, arg = -1, 0
-            else:
-                if len(spec) < 2 or len(spec) > (3 if fid >= 7 else 2):
-                    raise ValueError(f"window spec {spec!r}: expected ({fn!r}, column" +
-                                     (", offset)" if fid >= 7 else ")"))
-                col = self._resolve_column(spec[1])
-                arg = int(spec[2]) if len(spec) == 3 else (1 if fid >= 7 else 0)
+            fid, col, arg = self._window_spec(spec)
             ids.append(fid)
             cols.append(col)
             args.append(arg)
             names.append("" if name is None else str(name))
         return part, order, asc, ids, cols, args, names
+
+    def _window_frame_args(self, partition_by, order_by, ascending, funcs):
+        """_window_args plus the three frame lists, for a call with at least one rolling spec"""
+        part, order, asc = self._window_keys(partition_by, order_by, ascending)
+        ids, cols, args, names, pre, fol, minp = [], [], [], [], [], [], []
+        for name, spec in (funcs or {}).items():
+            if self._is_rolling(spec):
+                fid, col, p, f, m = self._rolling_spec(spec)
+                arg = 0
+            else:
+                (fid, col, arg), (p, f, m) = self._window_spec(spec), (0, 0, 1)
+            for lst, v in ((ids, fid), (cols, col), (args, arg), (names, "" if name is None else str(name)),
+                           (pre, p), (fol, f), (minp, m)):
+                lst.append(v)
+        return part, order, asc, ids, cols, args, names, pre, fol, minp
 
     def window(self, partition_by=None, order_by=None, ascending: Union[bool, List[bool]] = True,
                funcs: dict = None) -> "Table":
@@ -409,13 +448,25 @@ class Table(PandasOpsMixin):
         CURRENT ROW: this table's columns in its row order plus one column per entry of `funcs`, a dict
         from output name to "row_number" | "rank" | "dense_rank" | ("cumcount" | "cumsum" | "cummin" |
         "cummax", column) | ("lag" | "lead", column[, offset = 1]).  Ties keep row order; NaN sorts
-        after every number and null after NaN in both directions (docs/semantics.md "Window functions")."""
+        after every number and null after NaN in both directions (docs/semantics.md "Window functions").
+
+        Rolling aggregates take a frame of their own, ROWS BETWEEN preceding PRECEDING AND following
+        FOLLOWING of the partition: ("rolling_sum" | "rolling_mean" | "rolling_min" | "rolling_max" |
+        "rolling_count", column, preceding, following[, min_periods = 1]), None meaning unbounded, e.g.
+        ("rolling_mean", "v", 6, 0) for a 7-row moving average.  Nulls are skipped; the result is null
+        where the frame holds fewer than min_periods values (rolling_count is never null)."""
+        if any(self._is_rolling(s) for s in (funcs or {}).values()):
+            return self._wrap(C.window_frames(self._t, *self._window_frame_args(partition_by, order_by, ascending,
+                                                                                 funcs)))
         return self._wrap(C.window(self._t, *self._window_args(partition_by, order_by, ascending, funcs)))
 
     def distributed_window(self, partition_by=None, order_by=None, ascending: Union[bool, List[bool]] = True,
                            funcs: dict = None) -> "Table":
         """window() after a shuffle by the partition columns (at least one when the world is larger than
-        1); the output row order is unspecified."""
+        1); the output row order is unspecified.  Rolling specs as in window()."""
+        if any(self._is_rolling(s) for s in (funcs or {}).values()):
+            return self._wrap(C.distributed_window_frames(
+                self._t, *self._window_frame_args(partition_by, order_by, ascending, funcs)))
         return self._wrap(C.distributed_window(self._t, *self._window_args(partition_by, order_by, ascending, funcs)))
 
     def shuffle(self, hash_columns: List = None) -> "Table":

@@ -405,7 +405,9 @@ class DataFrame(object):
     def window(self, partition_by=None, order_by=None, ascending: Union[bool, List[bool]] = True, funcs: dict = None,
                env: CylonEnv = None) -> "DataFrame":
         """Window functions (Table.window): ranking, running aggregates and lag / lead per partition, e.g.
-        funcs={"rn": "row_number", "bal": ("cumsum", "amount"), "prev": ("lag", "amount", 1)}.  With an env
+        funcs={"rn": "row_number", "bal": ("cumsum", "amount"), "prev": ("lag", "amount", 1)}, and rolling
+        aggregates over a ROWS frame, e.g. {"avg7": ("rolling_mean", "amount", 6, 0)} (the pandas
+        groupby().rolling(7, min_periods=1).mean()); a bound of None is unbounded.  With an env
         of more than one rank the rows are first shuffled by the partition columns."""
         if env is None or env.world_size <= 1:
             return DataFrame(self._table.window(partition_by, order_by, ascending, funcs))

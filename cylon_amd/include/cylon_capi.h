@@ -58,6 +58,16 @@ int cylon_window(const char *table_id, const int32_t *partition_columns, int npa
                  const int32_t *order_columns, const int32_t *ascending, int norder, const int32_t *funcs,
                  const int32_t *spec_columns, const int64_t *spec_args, const char *const *names, int nspecs,
                  int distributed, const char *dest_id);
+/* cylon_window with a frame per spec: also funcs[i] = 9 ROLLING_COUNT, 10 ROLLING_SUM, 11 ROLLING_MEAN,
+   12 ROLLING_MIN, 13 ROLLING_MAX over ROWS BETWEEN preceding[i] PRECEDING AND following[i] FOLLOWING of
+   the partition (>= 0; INT64_MAX, or anything >= the row count: unbounded), null where the frame
+   holds fewer than min_periods[i] (>= 1) non-null values.  preceding / following NULL: 0;
+   min_periods NULL: 1.  Functions 0..8 ignore the three arrays. */
+int cylon_window_frames(const char *table_id, const int32_t *partition_columns, int npartition,
+                        const int32_t *order_columns, const int32_t *ascending, int norder, const int32_t *funcs,
+                        const int32_t *spec_columns, const int64_t *spec_args, const int64_t *preceding,
+                        const int64_t *following, const int64_t *min_periods, const char *const *names, int nspecs,
+                        int distributed, const char *dest_id);
 int cylon_project(const char *table_id, const int32_t *columns, int ncolumns, const char *dest_id);
 
 int cylon_merge(const char *const *table_ids, int ntables, const char *dest_id);

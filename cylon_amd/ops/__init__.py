@@ -61,6 +61,9 @@ def distributed_topk(t: Table, k: int, order_by=None, ascending: Union[bool, Lis
 
 def window(t: Table, partition_by=None, order_by=None, ascending: Union[bool, List[bool]] = True,
            funcs: dict = None) -> Table:
+    """Table.window: ranking, running aggregates, lag / lead and rolling aggregates over a ROWS frame,
+    ("rolling_sum" | "rolling_mean" | "rolling_min" | "rolling_max" | "rolling_count", column, preceding,
+    following[, min_periods])."""
     return t.window(partition_by, order_by, ascending, funcs)
 
 

@@ -80,6 +80,9 @@ int main(int argc, char **argv) {
   CHECK_OK(cylon::Window(a, {0}, {1}, {true},
                          {{cylon::WIN_ROW_NUMBER, -1, 0, "rn"}, {cylon::WIN_CUMSUM, 1, 0, "running"}}, win));
   report("window", win);
+  // the 3-row moving mean: AVG(column 1) OVER (... ROWS BETWEEN 2 PRECEDING AND CURRENT ROW)
+  CHECK_OK(cylon::Window(a, {0}, {1}, {true}, {{cylon::WIN_ROLLING_MEAN, 1, 0, "moving", 2, 0, 1}}, win));
+  report("window_frames", win);
   CHECK_OK(cylon::DistributedHashGroupBy(a, {0}, {1}, {cylon::AGG_SUM}, g));
   report("groupby_sum", g);
   CHECK_OK(cylon::compute::Sum(a, 1, sum));
