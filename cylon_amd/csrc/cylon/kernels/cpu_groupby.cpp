@@ -4,6 +4,7 @@
 #include <limits>
 
 #include "kernels.hpp"
+#include "order_image.hpp"
 #include "../hash.hpp"
 #include "../types.hpp"
 
@@ -36,17 +37,8 @@ inline int64_t extend(uint64_t b, int w, int kind) {
   return (int64_t)b;
 }
 
-inline uint64_t img(uint64_t bits, int w, int kind) {
-  const int nb = 8 * w;
-  const uint64_t mask = (nb == 64) ? ~0ull : ((1ull << nb) - 1);
-  const uint64_t sign = 1ull << (nb - 1);
-  bits &= mask;
-  if (kind == static_cast<int>(ValueKind::SIGNED_INT)) return bits ^ sign;
-  if (kind == static_cast<int>(ValueKind::FLOAT)) {
-    if (bits == sign) bits = 0;
-    return (bits & sign) ? (~bits & mask) : (bits | sign);
-  }
-  return bits;
+inline uint64_t img(const ColView &c, int64_t i) {
+  return order_image(load_bits(c.data, i, c.width), c.width, c.kind);
 }
 
 inline float half_to_float(uint16_t h) {
@@ -89,14 +81,9 @@ inline bool val_eq(const ColView &a, int64_t i, int64_t j) {
   }
   if (a.kind == static_cast<int>(ValueKind::FIXED_BYTES))
     return std::memcmp(a.data + i * a.width, a.data + j * a.width, a.width) == 0;
-  const int64_t x = extend(load_bits(a.data, i, a.width), a.width, a.kind);
-  const int64_t y = extend(load_bits(a.data, j, a.width), a.width, a.kind);
-  if (x == y) return true;
-  if (a.kind == static_cast<int>(ValueKind::FLOAT)) {
-    const double dx = as_double(a, i), dy = as_double(a, j);
-    return std::isnan(dx) && std::isnan(dy);
-  }
-  return false;
+  // the engine's value equality: equal order images (-0.0 == +0.0, NaN == NaN whatever the bits)
+  return order_image(load_bits(a.data, i, a.width), a.width, a.kind) ==
+         order_image(load_bits(a.data, j, a.width), a.width, a.kind);
 }
 }  // namespace
 
@@ -155,12 +142,12 @@ void agg_accumulate(const int64_t *gid, int64_t n, int64_t, const ColView &v, in
       case 0: fa[g] += as_double(v, i); break;
       case 1: ua[g] += (uint64_t)extend(load_bits(v.data, i, v.width), v.width, v.kind); break;
       case 2: {
-        const uint64_t x = img(load_bits(v.data, i, v.width), v.width, v.kind);
+        const uint64_t x = img(v, i);
         if (x < ua[g]) ua[g] = x;
         break;
       }
       case 3: {
-        const uint64_t x = img(load_bits(v.data, i, v.width), v.width, v.kind);
+        const uint64_t x = img(v, i);
         if (x > ua[g]) ua[g] = x;
         break;
       }
@@ -175,13 +162,8 @@ void agg_accumulate(const int64_t *gid, int64_t n, int64_t, const ColView &v, in
 }
 
 void agg_unimage(const uint64_t *in, int64_t m, int w, int kind, uint8_t *out, void *) {
-  const int nb = 8 * w;
-  const uint64_t mask = (nb == 64) ? ~0ull : ((1ull << nb) - 1);
-  const uint64_t sign = 1ull << (nb - 1);
   for (int64_t g = 0; g < m; ++g) {
-    uint64_t b = in[g] & mask;
-    if (kind == static_cast<int>(ValueKind::SIGNED_INT)) b ^= sign;
-    else if (kind == static_cast<int>(ValueKind::FLOAT)) b = (b & sign) ? (b ^ sign) : (~b & mask);
+    const uint64_t b = order_unimage(in[g], w, kind);
     std::memcpy(out + g * w, &b, w);
   }
 }

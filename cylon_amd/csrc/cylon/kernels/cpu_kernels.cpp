@@ -9,6 +9,7 @@
 #include <cmath>
 
 #include "kernels.hpp"
+#include "order_image.hpp"
 #include "../hash.hpp"
 #include "../types.hpp"
 
@@ -52,8 +53,9 @@ inline uint32_t partition_f(const ColView &c, int64_t i) {
   }
   if (c.kind == static_cast<int>(ValueKind::FIXED_BYTES))
     return hashing::murmur3_32(c.data + i * (int64_t)c.width, c.width, 0u);
-  const uint64_t bits = load_bits(c.data, i, c.width);
+  uint64_t bits = load_bits(c.data, i, c.width);
   if (c.kind == static_cast<int>(ValueKind::FLOAT)) {
+    bits = canonical_float_bits(bits, c.width);  // equal values (-0.0 / +0.0, any two NaNs) meet on one rank
     switch (c.width) {
       case 2: return hashing::murmur3_32_u16((uint16_t)bits);
       case 4: return hashing::murmur3_32_u32((uint32_t)bits);
@@ -456,24 +458,6 @@ void mask_to_indices(const uint8_t *mask, int64_t n, bool invert, int64_t *, int
 void iota(int64_t *out, int64_t n, int64_t start, void *) {
   for (int64_t i = 0; i < n; ++i) out[i] = start + i;
 }
-
-namespace {
-inline uint64_t order_image(uint64_t bits, int w, int kind) {
-  const int nb = 8 * w;
-  const uint64_t mask = (nb == 64) ? ~0ull : ((1ull << nb) - 1);
-  const uint64_t sign = 1ull << (nb - 1);
-  bits &= mask;
-  if (kind == static_cast<int>(ValueKind::SIGNED_INT)) return bits ^ sign;
-  if (kind == static_cast<int>(ValueKind::FLOAT)) {
-    if (bits == sign) bits = 0;
-    const uint64_t exp_mask = (w == 8) ? 0x7ff0000000000000ull : (w == 4 ? 0x7f800000ull : 0x7c00ull);
-    const uint64_t man_mask = (w == 8) ? 0x000fffffffffffffull : (w == 4 ? 0x007fffffull : 0x03ffull);
-    if ((bits & exp_mask) == exp_mask && (bits & man_mask) != 0) bits = exp_mask | ((man_mask + 1) >> 1);
-    return (bits & sign) ? (~bits & mask) : (bits | sign);
-  }
-  return bits;
-}
-}  // namespace
 
 void sort_keys_from_column(const ColView &c, const int64_t *perm, int64_t n, bool desc, uint64_t *out, void *) {
   const int nb = 8 * c.width;

@@ -21,6 +21,7 @@
 //   * scalar reductions (ngroups == 1): registers -> wave64 shuffle tree ->
 //     LDS -> one atomic per block.
 #include "device_common.hpp"
+#include "order_image.hpp"
 
 namespace cylon {
 namespace hip {
@@ -138,20 +139,9 @@ __device__ __forceinline__ bool val_eq(const ColView &a, int64_t i, int64_t j) {
       if (a.data[i * a.width + k] != a.data[j * a.width + k]) return false;
     return true;
   }
-  const int64_t x = extend_bits(load_bits(a.data, i, a.width), a.width, a.kind);
-  const int64_t y = extend_bits(load_bits(a.data, j, a.width), a.width, a.kind);
-  if (x == y) return true;
-  if (a.kind == static_cast<int>(ValueKind::FLOAT)) {  // NaN == NaN for grouping
-    if (a.width == 8) {
-      const double dx = __longlong_as_double(x), dy = __longlong_as_double(y);
-      return dx != dx && dy != dy;
-    }
-    if (a.width == 4) {
-      const float fx = __int_as_float((int)x), fy = __int_as_float((int)y);
-      return fx != fx && fy != fy;
-    }
-  }
-  return false;
+  // the engine's value equality: equal order images (-0.0 == +0.0, NaN == NaN whatever the bits)
+  return order_image(load_bits(a.data, i, a.width), a.width, a.kind) ==
+         order_image(load_bits(a.data, j, a.width), a.width, a.kind);
 }
 
 __global__ void k_segment_heads(ColSet3 cols, int ncols, const int64_t *__restrict__ perm, int64_t n,
@@ -180,17 +170,9 @@ void segment_heads(const ColView *cols, int ncols, const int64_t *perm, int64_t 
 // ---------------------------------------------------------------------------
 // aggregation
 // ---------------------------------------------------------------------------
-__device__ __forceinline__ uint64_t img(uint64_t bits, int w, int kind) {
-  const int nb = 8 * w;
-  const uint64_t mask = (nb == 64) ? ~0ull : ((1ull << nb) - 1);
-  const uint64_t sign = 1ull << (nb - 1);
-  bits &= mask;
-  if (kind == static_cast<int>(ValueKind::SIGNED_INT)) return bits ^ sign;
-  if (kind == static_cast<int>(ValueKind::FLOAT)) {
-    if (bits == sign) bits = 0;
-    return (bits & sign) ? (~bits & mask) : (bits | sign);
-  }
-  return bits;
+// MIN / MAX accumulate order images (order_image.hpp: -0.0 folded, every NaN the largest value)
+__device__ __forceinline__ uint64_t img(const ColView &c, int64_t i) {
+  return order_image(load_bits(c.data, i, c.width), c.width, c.kind);
 }
 
 __device__ __forceinline__ double as_double(const ColView &c, int64_t i) {
@@ -214,9 +196,9 @@ __device__ __forceinline__ void acc_global(void *acc, int64_t g, const ColView &
   if (KIND == 0) atomicAdd(reinterpret_cast<double *>(acc) + g, as_double(v, i));
   if (KIND == 1) atomicAdd(reinterpret_cast<unsigned long long *>(acc) + g, (unsigned long long)as_i64(v, i));
   if (KIND == 2)
-    atomicMin(reinterpret_cast<unsigned long long *>(acc) + g, (unsigned long long)img(load_bits(v.data, i, v.width), v.width, v.kind));
+    atomicMin(reinterpret_cast<unsigned long long *>(acc) + g, (unsigned long long)img(v, i));
   if (KIND == 3)
-    atomicMax(reinterpret_cast<unsigned long long *>(acc) + g, (unsigned long long)img(load_bits(v.data, i, v.width), v.width, v.kind));
+    atomicMax(reinterpret_cast<unsigned long long *>(acc) + g, (unsigned long long)img(v, i));
   if (KIND == 4) atomicAdd(reinterpret_cast<unsigned long long *>(acc) + g, 1ull);
   if (KIND == 5) {
     const double d = as_double(v, i) - mean[g];
@@ -248,8 +230,8 @@ __global__ __launch_bounds__(kBlock) void k_agg_lds(const int64_t *__restrict__ 
     const int64_t g = gid ? gid[i] : 0;
     if (KIND == 0) atomicAdd(reinterpret_cast<double *>(&lacc[g]), as_double(v, i));
     if (KIND == 1) atomicAdd(&lacc[g], (unsigned long long)as_i64(v, i));
-    if (KIND == 2) atomicMin(&lacc[g], (unsigned long long)img(load_bits(v.data, i, v.width), v.width, v.kind));
-    if (KIND == 3) atomicMax(&lacc[g], (unsigned long long)img(load_bits(v.data, i, v.width), v.width, v.kind));
+    if (KIND == 2) atomicMin(&lacc[g], (unsigned long long)img(v, i));
+    if (KIND == 3) atomicMax(&lacc[g], (unsigned long long)img(v, i));
     if (KIND == 4) atomicAdd(&lacc[g], 1ull);
     if (KIND == 5) {
       const double d = as_double(v, i) - mean[g];
@@ -290,11 +272,11 @@ __global__ __launch_bounds__(kBlock) void k_agg_scalar(int64_t n, ColView v, voi
     if (KIND == 1) us += (unsigned long long)as_i64(v, i);
     if (KIND == 4) us += 1;
     if (KIND == 2) {
-      const unsigned long long x = img(load_bits(v.data, i, v.width), v.width, v.kind);
+      const unsigned long long x = img(v, i);
       us = x < us ? x : us;
     }
     if (KIND == 3) {
-      const unsigned long long x = img(load_bits(v.data, i, v.width), v.width, v.kind);
+      const unsigned long long x = img(v, i);
       us = x > us ? x : us;
     }
   }
@@ -360,14 +342,9 @@ void agg_accumulate(const int64_t *gid, int64_t n, int64_t ngroups, const ColVie
 
 // images -> values of the original type (in place into out, width w)
 __global__ void k_unimg(const uint64_t *__restrict__ in, int64_t m, int w, int kind, uint8_t *__restrict__ out) {
-  const int nb = 8 * w;
-  const uint64_t mask = (nb == 64) ? ~0ull : ((1ull << nb) - 1);
-  const uint64_t sign = 1ull << (nb - 1);
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; g < m; g += stride) {
-    uint64_t b = in[g] & mask;
-    if (kind == static_cast<int>(ValueKind::SIGNED_INT)) b ^= sign;
-    else if (kind == static_cast<int>(ValueKind::FLOAT)) b = (b & sign) ? (b ^ sign) : (~b & mask);
+    const uint64_t b = order_unimage(in[g], w, kind);
     switch (w) {
       case 1: out[g] = (uint8_t)b; break;
       case 2: reinterpret_cast<uint16_t *>(out)[g] = (uint16_t)b; break;

@@ -1,6 +1,8 @@
-// Order images of fixed-width values: the one definition shared by the sort (sort.hip k_sort_keys),
-// the top-k select (topk.hip) and the select's CPU twin (cpu_topk.cpp).  Unsigned order of the
-// images = the requested order of the values, so the select and the sort agree by construction.
+// Order images of fixed-width values: the one definition shared by the sort (sort.hip k_sort_keys
+// and its CPU twin), the top-k select (topk.hip, cpu_topk.cpp), the window / rolling MIN and MAX and
+// the group-by's and scalar MIN / MAX (groupby.hip, radix_groupby.hip, cpu_groupby.cpp).  Unsigned
+// order of the images = the requested order of the values, so all of them agree by construction.
+// Equal images = equal values under the engine's value equality (-0.0 == +0.0, every NaN one value).
 #pragma once
 #include <cstdint>
 
@@ -40,6 +42,12 @@ CYLON_HD uint64_t order_unimage(uint64_t img, int w, int kind) {
   if (kind == static_cast<int>(ValueKind::SIGNED_INT)) return img ^ sign;
   if (kind == static_cast<int>(ValueKind::FLOAT)) return (img & sign) ? (img ^ sign) : (~img & mask);
   return img;
+}
+
+// the bits MIN / MAX give back for a float: -0.0 -> +0.0, every NaN -> the positive quiet NaN
+CYLON_HD uint64_t canonical_float_bits(uint64_t bits, int w) {
+  const int kind = static_cast<int>(ValueKind::FLOAT);
+  return order_unimage(order_image(bits, w, kind), w, kind);
 }
 
 CYLON_HD bool is_nan_bits(uint64_t bits, int w) {

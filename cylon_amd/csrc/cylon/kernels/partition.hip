@@ -18,6 +18,7 @@
 //     contiguous range: no pack step before the all-to-all.
 //   * scatter_columns: all fixed-width columns of a table in one launch,
 //     destination read once per row.
+#include "order_image.hpp"
 #include "stable_rank.hpp"
 
 namespace cylon {
@@ -43,8 +44,9 @@ __device__ __forceinline__ uint32_t partition_f(const ColView &c, int64_t i) {
   if (kind == static_cast<int>(ValueKind::FIXED_BYTES)) {
     return hashing::murmur3_32(c.data + i * (int64_t)c.width, c.width, 0u);
   }
-  const uint64_t bits = load_bits(c.data, i, c.width);
+  uint64_t bits = load_bits(c.data, i, c.width);
   if (kind == static_cast<int>(ValueKind::FLOAT)) {
+    bits = canonical_float_bits(bits, c.width);  // equal values (-0.0 / +0.0, any two NaNs) meet on one rank
     switch (c.width) {
       case 2: return hashing::murmur3_32_u16((uint16_t)bits);
       case 4: return hashing::murmur3_32_u32((uint32_t)bits);

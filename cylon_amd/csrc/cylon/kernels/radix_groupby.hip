@@ -22,6 +22,7 @@
 #include <cstdlib>
 
 #include "device_common.hpp"
+#include "order_image.hpp"
 
 namespace cylon {
 namespace hip {
@@ -94,19 +95,6 @@ struct RGArgs {
   int nacc;
   int has_m2;  // some accumulator is RG_M2: a second pass over the partition's rows
 };
-
-__device__ __forceinline__ uint64_t rg_img(uint64_t bits, int w, int kind) {
-  const int nb = 8 * w;
-  const uint64_t mask = (nb == 64) ? ~0ull : ((1ull << nb) - 1);
-  const uint64_t sign = 1ull << (nb - 1);
-  bits &= mask;
-  if (kind == static_cast<int>(ValueKind::SIGNED_INT)) return bits ^ sign;
-  if (kind == static_cast<int>(ValueKind::FLOAT)) {
-    if (bits == sign) bits = 0;
-    return (bits & sign) ? (~bits & mask) : (bits | sign);
-  }
-  return bits;
-}
 
 __device__ __forceinline__ double rg_double(uint64_t b, int w, int kind) {
   if (kind == static_cast<int>(ValueKind::FLOAT)) {
@@ -189,8 +177,8 @@ __global__ __launch_bounds__(kRGThreads) void k_rg_agg(const int64_t *__restrict
         switch (c.kind) {
           case RG_SUMF: atomicAdd(reinterpret_cast<double *>(t), rg_double(vb[j], c.width, c.vkind)); break;
           case RG_SUMI: atomicAdd(t, (unsigned long long)extend_bits(vb[j], c.width, c.vkind)); break;
-          case RG_MIN: atomicMin(t, (unsigned long long)rg_img(vb[j], c.width, c.vkind)); break;
-          case RG_MAX: atomicMax(t, (unsigned long long)rg_img(vb[j], c.width, c.vkind)); break;
+          case RG_MIN: atomicMin(t, (unsigned long long)order_image(vb[j], c.width, c.vkind)); break;
+          case RG_MAX: atomicMax(t, (unsigned long long)order_image(vb[j], c.width, c.vkind)); break;
           case RG_M2: break;  // second pass
           default: atomicAdd(t, 1ull);
         }
@@ -308,7 +296,7 @@ __global__ void k_rg_pack(const int64_t *__restrict__ offs, const int64_t *__res
 //      written per group at a slot from an LDS counter (gcount per partition; radix_groupby_pack
 //      packs the slabs).
 // Nulls rank after every value (excluded, as the global path does).  Values compare as
-// order-preserving images of their doubles (NaN canonicalised).
+// order-preserving images of their doubles (NaN canonicalised, -0.0 folded into +0.0).
 constexpr int kQCap = 4096, kQThreads = 512, kQPer = kQCap / kQThreads, kQBBits = 11, kQBuckets = 1 << kQBBits;
 constexpr int kQWaveRows = 128;  // buckets one wave sorts in registers (2 rows per lane)
 
@@ -331,6 +319,7 @@ __device__ __forceinline__ uint32_t q_block_exscan(uint32_t c, uint32_t *wsum) {
 
 __device__ __forceinline__ uint64_t q_image(double d) {
   uint64_t b = (uint64_t)__double_as_longlong(d != d ? __longlong_as_double(0x7ff8000000000000ll) : d);
+  if (b == 0x8000000000000000ull) b = 0;  // -0.0 == +0.0: the fused MIN / MAX give +0.0, as order_image does
   return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
 }
 __device__ __forceinline__ double q_unimage(uint64_t m) {

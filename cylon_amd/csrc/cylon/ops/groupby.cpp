@@ -72,6 +72,11 @@ GroupInfo GroupIds(const TablePtr &t, const std::vector<int> &cols, bool presort
     at::Tensor keys;
     if (c.type.width() == 8 && c.type.kind() == ValueKind::SIGNED_INT) {
       keys = c.data.view(at::kLong);
+    } else if (c.type.kind() == ValueKind::FLOAT) {
+      // the ascending sort image: one key per value under the value equality (-0.0 == +0.0, every
+      // NaN one value whatever its sign or payload), at every float width
+      keys = ex.empty_i64(n);
+      KCALL(ex, sort_keys_from_column, c.view(), nullptr, n, false, reinterpret_cast<uint64_t *>(ptr<int64_t>(keys)));
     } else {
       keys = ex.empty_i64(n);
       KCALL(ex, key64_from_column, c.view(), n, ptr<int64_t>(keys));

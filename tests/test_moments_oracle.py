@@ -60,13 +60,11 @@ import pytest
 from cylon_amd import Table
 from cylon_amd._lib import C
 
-from dist_utils import run_distributed
+from oracle_utils import INT64_MIN, LADDER, deal_round_robin, spawn_once, traced, wide_keys
 
 U = Fraction(1, 1 << 53)
-INT64_MIN = -(1 << 63)
 
 CLASSES = ("offset", "offset6", "const", "mixed", "float32", "int64_big", "int8")
-LADDER = (1, 2, 3, 63, 64, 65, 255, 256, 257, 1000)
 ONE_GROUP = (1, 65, 4097)
 
 Stats = collections.namedtuple("Stats", "n S mu M2 A I")  # I: the exact sum of integer values
@@ -186,28 +184,19 @@ def _second_class(cls):
 
 
 # ---- data: shapes (group sizes and keys)
-def _wide_keys(rng, count):
-    """distinct int64 keys of both signs with the high half set, none INT64_MIN"""
-    keys = set()
-    while len(keys) < count:
-        k = int(rng.integers(1 << 40, 1 << 62)) * (1 if len(keys) % 2 else -1)
-        keys.add(k)
-    return sorted(keys, key=lambda k: (abs(k) % 1009, k))
-
-
 def _shape_keys(shape, rng):
     """(key of each row, the key whose values are all null or None)"""
     if shape.startswith("one_group_"):
         return np.full(int(shape.rsplit("_", 1)[1]), 42, dtype=np.int64), None
     if shape == "hot":
-        keys = _wide_keys(rng, 501)
+        keys = wide_keys(rng, 501)
         return np.concatenate([np.full(5000, keys[0]), keys[1:]]).astype(np.int64), keys[7]
     if shape == "two_keys":  # a span of 42 bits: with the int16 field an exact composite key
         keys = (rng.choice(np.arange(-(1 << 20), 1 << 20), len(LADDER) + 1, replace=False) << 20).tolist()
         return np.repeat(np.array(keys, dtype=np.int64), list(LADDER) + [5]), keys[-1]
     assert shape in ("ladder", "many", "nullable_key")
     extra = 2100 if shape == "many" else 0
-    keys = _wide_keys(rng, len(LADDER) + 1 + extra)
+    keys = wide_keys(rng, len(LADDER) + 1 + extra)
     sizes = list(LADDER) + [5] + [1 + i % 6 for i in range(extra)]
     keys.append(INT64_MIN)  # the radix table's spare slot; the global path's sentinel slot
     sizes.append(100)
@@ -453,12 +442,7 @@ def _dist_worker(ctx, cases, chunks, forced):
     C.trace_reset()
     for shape, cls, form in cases:
         t, keys = dataset(shape, cls, form == "generic")
-        seen, mine = {}, []
-        for i, kk in enumerate(zip(*[t[c].to_pylist() for c in keys])):
-            j = seen.get(kk, 0)
-            seen[kk] = j + 1
-            if j % world == rank:
-                mine.append(i)
+        mine = deal_round_robin(zip(*[t[c].to_pylist() for c in keys]), rank, world)
         T = Table(t.take(pa.array(mine, type=pa.int64())), ctx)
         assert T.device == ctx.device
         out[(shape, cls, form)] = _columns(T.groupby(list(keys), ALL_AGGS if form == "generic" else FAST_AGGS))
@@ -467,28 +451,21 @@ def _dist_worker(ctx, cases, chunks, forced):
     return out, counters
 
 
-_spawned = {}
+_spawned, _merged = {}, {}
 
 
 def _dist_results(world, device, chunks, rccl_forced=False):
     """One spawn per configuration, ever (a failed spawn is remembered, not repeated);
     (case -> result columns concatenated over the ranks, counters of every rank)."""
     cfg = (world, device, chunks, rccl_forced)
-    if cfg not in _spawned:
-        env = {"CYLON_TEST_COMM": "rccl"} if rccl_forced else None
-        try:
-            res = run_distributed(_dist_worker, world, DIST_CASES, chunks, rccl_forced, device=device, env=env)
-        except BaseException as e:
-            _spawned[cfg] = e
-            raise
+    res = spawn_once(_spawned, _dist_worker, DIST_CASES, world, device, chunks, rccl_forced)
+    if cfg not in _merged:
         merged = {}
         for case in DIST_CASES:
             parts = [r[0][case] for r in res]
             merged[case] = [sum((p[i] for p in parts), []) for i in range(len(parts[0]))]
-        _spawned[cfg] = (merged, [r[1] for r in res])
-    if isinstance(_spawned[cfg], BaseException):
-        raise AssertionError(f"the ranks of {cfg} failed before: {_spawned[cfg]!r}")
-    return _spawned[cfg]
+        _merged[cfg] = (merged, [r[1] for r in res])
+    return _merged[cfg]
 
 
 def _check_dist(results, case, what):
@@ -507,15 +484,6 @@ def test_cpu_distributed_groupby_matches_oracle(world, chunks, case):
 
 
 # ---- GPU
-def _traced(fn):
-    C.trace_enable(True)
-    C.trace_reset()
-    try:
-        return fn(), dict(C.trace_counters())
-    finally:
-        C.trace_enable(False)
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("shape,cls", GROUPED + SINGLE, ids=_ids(GROUPED + SINGLE))
 def test_gpu_global_path_matches_oracle(gpu_ctx, monkeypatch, shape, cls):
@@ -524,7 +492,7 @@ def test_gpu_global_path_matches_oracle(gpu_ctx, monkeypatch, shape, cls):
     monkeypatch.setenv("CYLON_RADIX_GROUPBY_MIN_ROWS", str(1 << 62))
     t, keys = dataset(shape, cls)
     T = Table(t, gpu_ctx)
-    got, cnt = _traced(lambda: T.local_groupby(list(keys), ALL_AGGS))
+    got, cnt = traced(lambda: T.local_groupby(list(keys), ALL_AGGS))
     assert "groupby.radix.groups" not in cnt, cnt
     check(_columns(got), ALL_AGGS, shape, cls, "gpu global")
 
@@ -547,7 +515,7 @@ def test_gpu_radix_path_matches_oracle(gpu_ctx, monkeypatch, shape, cls, planes)
     t, keys = dataset(shape, cls)
     aggs = RADIX_AGGS[planes]
     T = Table(t, gpu_ctx)
-    got, cnt = _traced(lambda: T.local_groupby(list(keys), aggs))
+    got, cnt = traced(lambda: T.local_groupby(list(keys), aggs))
     assert cnt.get("groupby.radix.groups") == len(expected(shape, cls, True, "x")), cnt
     assert cnt.get("groupby.radix.overflow_fallback", 0) == 0, cnt
     check(_columns(got), aggs, shape, cls, f"gpu radix {planes} planes")
