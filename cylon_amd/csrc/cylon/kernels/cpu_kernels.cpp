@@ -69,6 +69,12 @@ inline void move_any(const uint8_t *src, int64_t si, uint8_t *dst, int64_t di, i
   std::memcpy(dst + di * w, src + si * w, w);
 }
 
+// twin of hash_join.hip join_key_bits: floats through canonical_float_bits (order_image.hpp)
+inline int64_t join_key_bits(uint64_t b, int w, int kind) {
+  if (kind == static_cast<int>(ValueKind::FLOAT)) return (int64_t)canonical_float_bits(b, w);
+  return extend_bits(b, w, kind);
+}
+
 inline uint64_t value_hash64(const ColView &c, int64_t i) {
   if (c.valid != nullptr && c.valid[i] == 0) return 0x5bd1e9955bd1e995ULL;
   if (c.kind == static_cast<int>(ValueKind::VAR_BYTES)) {
@@ -78,7 +84,7 @@ inline uint64_t value_hash64(const ColView &c, int64_t i) {
   if (c.kind == static_cast<int>(ValueKind::FIXED_BYTES)) {
     return hashing::bytes_hash64(c.data + i * (int64_t)c.width, c.width);
   }
-  return hashing::fmix64((uint64_t)extend_bits(load_bits(c.data, i, c.width), c.width, c.kind));
+  return hashing::fmix64((uint64_t)join_key_bits(load_bits(c.data, i, c.width), c.width, c.kind));
 }
 
 inline bool value_equal(const ColView &a, int64_t i, const ColView &b, int64_t j) {
@@ -92,24 +98,8 @@ inline bool value_equal(const ColView &a, int64_t i, const ColView &b, int64_t j
   }
   if (a.kind == static_cast<int>(ValueKind::FIXED_BYTES))
     return std::memcmp(a.data + i * a.width, b.data + j * b.width, a.width) == 0;
-  const int64_t x = extend_bits(load_bits(a.data, i, a.width), a.width, a.kind);
-  const int64_t y = extend_bits(load_bits(b.data, j, b.width), b.width, b.kind);
-  if (a.kind == static_cast<int>(ValueKind::FLOAT)) {
-    if (a.width == 8) {
-      double dx, dy;
-      std::memcpy(&dx, &x, 8);
-      std::memcpy(&dy, &y, 8);
-      return dx == dy || (std::isnan(dx) && std::isnan(dy));
-    }
-    if (a.width == 4) {
-      float fx, fy;
-      uint32_t ux = (uint32_t)x, uy = (uint32_t)y;
-      std::memcpy(&fx, &ux, 4);
-      std::memcpy(&fy, &uy, 4);
-      return fx == fy || (std::isnan(fx) && std::isnan(fy));
-    }
-  }
-  return x == y;
+  return join_key_bits(load_bits(a.data, i, a.width), a.width, a.kind) ==
+         join_key_bits(load_bits(b.data, j, b.width), b.width, b.kind);
 }
 
 }  // namespace
@@ -266,7 +256,7 @@ void row_hash64(const ColView *cols, int ncols, int64_t n, uint64_t *out, void *
 }
 
 void key64_from_column(const ColView &col, int64_t n, int64_t *out, void *) {
-  for (int64_t i = 0; i < n; ++i) out[i] = extend_bits(load_bits(col.data, i, col.width), col.width, col.kind);
+  for (int64_t i = 0; i < n; ++i) out[i] = join_key_bits(load_bits(col.data, i, col.width), col.width, col.kind);
 }
 
 void composite_key_pack(const ColView *cols, int nk, const int64_t *lo, const int *shift, int64_t n, int64_t *out,

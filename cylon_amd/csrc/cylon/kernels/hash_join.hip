@@ -13,6 +13,7 @@
 // order (deterministic output).  Multi-column, nullable and var-width keys are
 // reduced to a 64-bit row hash first; candidate pairs are then confirmed by
 // rows_equal (null == null, pandas semantics).
+#include "order_image.hpp"
 #include "radix_pass.hpp"
 
 namespace cylon {
@@ -245,6 +246,14 @@ void hash_probe_emit(const int64_t *keys, int64_t n, HashTableRef t, int64_t cap
 // ---------------------------------------------------------------------------
 // generic keys
 // ---------------------------------------------------------------------------
+// The 64-bit join-key image of a fixed-width cell: equal images <=> equal values under the engine's
+// value equality.  Floats go through the one definition of it (order_image.hpp): -0.0 is +0.0 and
+// every NaN, whatever its sign bit or payload, is the quiet NaN; integers are sign- / zero-extended.
+__device__ __forceinline__ int64_t join_key_bits(uint64_t b, int w, int kind) {
+  if (kind == static_cast<int>(ValueKind::FLOAT)) return (int64_t)canonical_float_bits(b, w);
+  return extend_bits(b, w, kind);
+}
+
 __device__ __forceinline__ uint64_t value_hash64(const ColView &c, int64_t i) {
   if (c.valid != nullptr && c.valid[i] == 0) return 0x5bd1e9955bd1e995ULL;  // null token
   if (c.kind == static_cast<int>(ValueKind::VAR_BYTES)) {
@@ -254,7 +263,7 @@ __device__ __forceinline__ uint64_t value_hash64(const ColView &c, int64_t i) {
   if (c.kind == static_cast<int>(ValueKind::FIXED_BYTES)) {
     return hashing::bytes_hash64(c.data + i * (int64_t)c.width, c.width);
   }
-  return hashing::fmix64((uint64_t)extend_bits(load_bits(c.data, i, c.width), c.width, c.kind));
+  return hashing::fmix64((uint64_t)join_key_bits(load_bits(c.data, i, c.width), c.width, c.kind));
 }
 
 __global__ void k_row_hash64(ColSet2 cols, int ncols, int64_t n, uint64_t *__restrict__ out) {
@@ -278,7 +287,7 @@ void row_hash64(const ColView *cols, int ncols, int64_t n, uint64_t *out, void *
 __global__ void k_key64(ColView c, int64_t n, int64_t *__restrict__ out) {
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride)
-    out[i] = extend_bits(load_bits(c.data, i, c.width), c.width, c.kind);
+    out[i] = join_key_bits(load_bits(c.data, i, c.width), c.width, c.kind);
 }
 
 void key64_from_column(const ColView &col, int64_t n, int64_t *out, void *stream) {
@@ -414,19 +423,8 @@ __device__ __forceinline__ bool value_equal(const ColView &a, int64_t i, const C
       if (a.data[i * w + k] != b.data[j * w + k]) return false;
     return true;
   }
-  const int64_t x = extend_bits(load_bits(a.data, i, a.width), a.width, a.kind);
-  const int64_t y = extend_bits(load_bits(b.data, j, b.width), b.width, b.kind);
-  if (a.kind == static_cast<int>(ValueKind::FLOAT)) {
-    if (a.width == 8) {
-      const double dx = __longlong_as_double(x), dy = __longlong_as_double(y);
-      return dx == dy || (dx != dx && dy != dy);
-    }
-    if (a.width == 4) {
-      const float fx = __int_as_float((int)x), fy = __int_as_float((int)y);
-      return fx == fy || (fx != fx && fy != fy);
-    }
-  }
-  return x == y;
+  return join_key_bits(load_bits(a.data, i, a.width), a.width, a.kind) ==
+         join_key_bits(load_bits(b.data, j, b.width), b.width, b.kind);
 }
 
 __global__ void k_rows_equal(ColSet2 l, ColSet2 r, int ncols, const int64_t *__restrict__ li,

@@ -40,11 +40,13 @@ import pytest
 from cylon_amd import Table
 from cylon_amd._lib import C
 
-from oracle_utils import INT64_MIN, LADDER, deal_round_robin, spawn_once, traced, wide_keys
+from oracle_utils import FLOAT_FIELDS as _FLOAT_FIELDS
+from oracle_utils import width_kind as _wk
+from oracle_utils import (INT64_MIN, LADDER, column_bits, deal_round_robin, fspecials, make_array, spawn_once, traced,
+                          wide_keys)
 
 Expect = collections.namedtuple("Expect", "min max nunique count")  # min / max: bits, or None for null
 
-_FLOAT_FIELDS = {2: (5, 10), 4: (8, 23), 8: (11, 52)}  # width -> (exponent bits, mantissa bits)
 _FLOAT_FMT = {2: "<e", 4: "<f", 8: "<d"}
 
 
@@ -102,13 +104,6 @@ def fbits(x, w):
     return int.from_bytes(struct.pack(_FLOAT_FMT[w], x), "little")
 
 
-def fspecials(w):
-    e, m = _FLOAT_FIELDS[w]
-    S, E = 1 << (8 * w - 1), ((1 << e) - 1) << m
-    return dict(pnan=E | 1 << (m - 1), nnan=S | E | 1 << (m - 1), psnan=E | 1, nsnan=S | E | 1, pinf=E, ninf=S | E,
-                pzero=0, nzero=S, pden=1, nden=S | 1, pmax=E - 1, nmax=S | (E - 1))
-
-
 def test_oracle_on_nan_free_data_is_python_min_max_set():
     rng = np.random.default_rng(5)
     for w, kind in [(2, "f"), (4, "f"), (8, "f"), (1, "i"), (2, "u"), (4, "i"), (8, "i"), (8, "u"), (1, "u")]:
@@ -155,38 +150,6 @@ def test_oracle_hand_table():
 
 
 # ---- arrow columns <-> bit patterns
-def _wk(typ):
-    if pa.types.is_boolean(typ):
-        return 1, "u"
-    kind = "f" if pa.types.is_floating(typ) else ("i" if pa.types.is_signed_integer(typ) else "u")
-    return typ.bit_width // 8, kind
-
-
-def column_bits(col):
-    """bit pattern of every row (None for null), read from the column's data buffer"""
-    a = col.combine_chunks() if isinstance(col, pa.ChunkedArray) else col
-    if isinstance(a, pa.ChunkedArray):  # (older pyarrow: a chunked array of one chunk)
-        a = a.chunk(0) if a.num_chunks else pa.array([], type=a.type)
-    if pa.types.is_boolean(a.type):
-        return [None if v is None else int(v) for v in a.to_pylist()]
-    w = a.type.bit_width // 8
-    raw = a.buffers()[1].to_pybytes() if a.buffers()[1] is not None else b""
-    valid = a.is_valid().to_pylist()
-    return [int.from_bytes(raw[(a.offset + i) * w:(a.offset + i + 1) * w], "little") if valid[i] else None
-            for i in range(len(a))]
-
-
-def make_array(bits, typ, nullable):
-    w, kind = _wk(typ)
-    raw = np.array([0 if b is None else b for b in bits], dtype=f"u{w}")
-    vals = raw.astype(bool) if pa.types.is_boolean(typ) else (raw.view(f"f{w}") if kind == "f" else
-                                                                 (raw.view(f"i{w}") if kind == "i" else raw))
-    if not nullable:
-        assert None not in bits
-        return pa.array(vals, type=typ)
-    return pa.array(vals, type=typ, mask=np.array([b is None for b in bits], dtype=bool))
-
-
 def _ident(col):
     """what makes two key rows one group: the image of a float key, the value of any other; None = null"""
     if pa.types.is_floating(col.type):
