@@ -15,6 +15,7 @@
 #include "cylon/knobs.hpp"
 #include "cylon/ops/api_ext.hpp"
 #include "cylon/ops/graph.hpp"
+#include "cylon/ops/radix_sizing.hpp"
 #include "cylon/ops/relational.hpp"
 #include "cylon/ops/util.hpp"
 #include "cylon/table.hpp"
@@ -374,6 +375,11 @@ void register_extended_ops(py::module &m) {
   m.def("window_carry_tiles", []() { return hip::window_carry_tiles(); });
   // the widest frame (preceding + following + 1) that the one-launch LDS kernel of kernels/rolling.hip takes
   m.def("window_frame_lds_rows", []() { return hip::window_frame_lds_rows(); });
+  // the radix partitions' sizing rules (ops/radix_sizing.hpp): partition bits of `rows` build rows against
+  // an LDS capacity, and the slot-mode rows per partition of `rows` rows in `nparts` partitions
+  m.def("radix_partition_bits", [](int64_t rows, int64_t cap) { return ops::sizing::partition_bits(rows, cap); });
+  m.def("radix_slot_rows",
+        [](int64_t rows, int64_t nparts) { return ops::sizing::slot_rows((double)rows / (double)nparts); });
   // ---- streaming op graph (C24) ------------------------------------------
   m.def(
       "dis_join_op",

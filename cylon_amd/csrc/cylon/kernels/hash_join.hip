@@ -296,7 +296,7 @@ void key64_from_column(const ColView &col, int64_t n, int64_t *out, void *stream
   HIP_LAUNCH_CHECK();
 }
 
-// K5 exact composite key of several integer key columns (ops/join.cpp radix_keys): one pass reads
+// K5 exact composite key of several integer key columns (ops/join_keys.cpp radix_keys): one pass reads
 // every key column at its own width and writes the packed int64 -- the LDS radix join then moves
 // ONE 8-byte key instead of the image plus each key column; unpack rebuilds the key columns of the
 // join output from the composite the kernel wrote (one read, one write per key column).

@@ -219,7 +219,7 @@ void radix_slot_rows_pass(const int64_t *keys, int64_t n, int total_bits, int fi
                           int64_t *ws, int64_t *counts, unsigned int *overflow, void *stream,
                           const NarrowKeys *nk = nullptr);
 /* Fixed-length strings (L bytes per row, row-major) <-> ceil(L / 8) <= 8 int64 word columns, and the
-   rows whose word columns differ while both rows are present (GPU only; ops/join.cpp) */
+   rows whose word columns differ while both rows are present (GPU only; ops/join_keys.cpp) */
 void var_len_minmax(const int64_t *offs, int64_t n, int64_t *mm, void *stream);  // mm[0..1] = min / max length
 // hash: the row_hash64 of the string (one key column); inv: hash = the invertible word key
 // (hash.hpp word_key_*) and word 0 is not written (words[0] unused)

@@ -239,7 +239,7 @@ struct BuildOut {               // build-side output columns
 
 // Outer joins (OJ bits, see rj_count_mark): presence bytes (ppres / bpres: 1 = that side holds a
 // row) are written for the side(s) that can be null; the host turns them into the output
-// columns' validity (join.cpp radix_join).
+// columns' validity (join_radix.cpp radix_join).
 
 // the write kernel's build staging: rj_dma_block over its 16 waves
 __device__ __forceinline__ void rj_dma(const uint8_t *src, int bytes, uint8_t *dst, int wave, int lane) {

@@ -340,7 +340,7 @@ void gather_var_bytes(const ColView &in, const int64_t *idx, int64_t m, const in
 }
 
 // ---------------------------------------------------------------------------
-// fixed-length strings <-> int64 word columns (ops/join.cpp: strings of L bytes travel through the
+// fixed-length strings <-> int64 word columns (ops/join_keys.cpp: strings of L bytes travel through the
 // radix join as ceil(L / 8) words); one row per thread, 8-byte accesses when L % 8 == 0
 // ---------------------------------------------------------------------------
 constexpr int kMaxWords = 8;

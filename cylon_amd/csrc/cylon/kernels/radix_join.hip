@@ -1893,7 +1893,7 @@ static void slot_rows_pass(const Digit &dg, int64_t n, int first_bits, int secon
   }
 }
 
-// Second pass of a bounded-memory join chunk (ops/join.cpp radix_join_chunked): the input is the
+// Second pass of a bounded-memory join chunk (ops/join_bounded.cpp radix_join_chunked): the input is the
 // chunk's rows of an exact narrowed first pass -- nseg consecutive first-pass buckets, bucket g
 // starting at row bbase[g] (relative to the chunk) -- and digit d = the low second_bits bits of the
 // total_bits partition id goes to slot g * 2^second_bits + d, so the chunk's partitions come out
@@ -2221,7 +2221,7 @@ void radix_part_offsets(const int64_t *keys, int64_t n, int bits, int64_t *offs,
   HIP_LAUNCH_CHECK();
 }
 
-// ---- key-hash chunks of the bounded-memory join (ops/join.cpp radix_join_chunked): chunk = the LOW
+// ---- key-hash chunks of the bounded-memory join (ops/join_bounded.cpp radix_join_chunked): chunk = the LOW
 // cbits bits of fmix64(key) -- independent of the join's partition, which takes the TOP bits -- so
 // every chunk's own radix join still spreads over all of its partitions.  One exact (XT) pass moves
 // every column into chunk-major order; chunk c is then rows [offs[c], offs[c + 1]).

@@ -2,7 +2,7 @@
 //
 // Semantics (docs/semantics.md, "Semi / anti join"): a left row survives a semi join iff some
 // right row has an equal key, and an anti join iff none has.  Only the keys take part: exact
-// int64 key images (ops/join.cpp radix_keys), so key equality is image equality.
+// int64 key images (ops/join_keys.cpp radix_keys), so key equality is image equality.
 //
 // MI355X design (no sort, no global hash table, no payload staging):
 //   1. the host radix-partitions the right keys (8 B/row) and the left (key, row id) pairs

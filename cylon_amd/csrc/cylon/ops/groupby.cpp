@@ -428,7 +428,7 @@ static TablePtr radix_groupby(const TablePtr &tin, const std::vector<int> &keys,
                               bool hash_strings = false) {
   const int64_t n = tin->Rows();
   if (!tin->device().is_cuda() || n < radix_groupby_min_rows()) return nullptr;
-  // A fixed-length string key groups by its invertible word key h (ops/join.cpp uses the same key):
+  // A fixed-length string key groups by its invertible word key h (ops/join_keys.cpp uses the same key):
   // equal h + equal words 1..W-1 means equal strings, so the words ride along as MIN and MAX
   // accumulators and the result is exact when MIN == MAX in every group (else: the exact path).
   // The output key bytes are rebuilt from h and the MIN words.

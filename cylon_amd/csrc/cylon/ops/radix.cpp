@@ -7,6 +7,7 @@
 
 #include <atomic>
 
+#include "radix_sizing.hpp"
 #include "util.hpp"
 #include "../trace.hpp"
 
@@ -223,7 +224,7 @@ std::vector<at::Tensor> RadixPartitionSlotted(const Exec &ex, std::vector<at::Te
               "RadixPartitionSlotted arguments");
   const int64_t n = cur[0].numel();
   // second (low) digit <= 9 bits, first (high) digit <= 10 bits: 11 .. 19 partition bits
-  const int db2 = std::min(9, bits / 2), db1 = bits - db2;
+  const auto [db1, db2] = sizing::digit_split(bits);
   if (bits < 2 || db1 > 10) return {};
   // (the block size of the unstable pass does not depend on the column count)
   if (!hip::radix_slot_eligible(n, (int)cur.size(), db1, db2)) return {};
@@ -237,7 +238,7 @@ std::vector<at::Tensor> RadixPartitionSlotted(const Exec &ex, std::vector<at::Te
                          : ex.empty_i64(hip::radix_rows_pass_workspace(n, db1));
   const int64_t nb1 = int64_t(1) << db1;
   const double mean1 = (double)n / (double)(8 * nb1);
-  const int64_t s1 = slot1 ? (((int64_t)(mean1 + 8.0 * std::sqrt(mean1) + 64.0) + 7) & ~int64_t(7)) : 0;
+  const int64_t s1 = slot1 ? sizing::slot_rows(mean1) : 0;
   const int64_t rows1 = slot1 ? 8 * nb1 * s1 + hip::radix_slot_tile_rows() : n;
   at::Tensor cnt1 = slot1 ? ex.empty_i64(8 * nb1) : at::Tensor();
   *overflow = at::zeros({1}, ex.opts(at::kInt));

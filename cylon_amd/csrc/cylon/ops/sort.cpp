@@ -15,6 +15,7 @@
 #include <atomic>
 #include <cmath>
 
+#include "radix_sizing.hpp"
 #include "util.hpp"
 #include "../trace.hpp"
 
@@ -151,20 +152,19 @@ static TablePtr radix_sort_keys_msd(const Exec &ex, const TablePtr &t, const Col
   // the keys fill [0, span) of the digits' [0, 2^hr): a bucket of an occupied range holds 1 / fill
   // times the mean (keys in [-3e6, 3e6) x 977 span 33 bits at fill 0.68)
   const double fill = std::max(0.5, (double)(img_max - img_min) / std::ldexp(1.0, hr));
-  auto slot_for = [](double mean) { return ((int64_t)(mean + 8.0 * std::sqrt(mean) + 64.0) + 7) & ~int64_t(7); };
   const int64_t cap = hip::seg_sort_capacity();
   auto mean_of = [&](int64_t buckets) { return (double)n / ((double)buckets * fill); };
   int bits = 11;
-  while (bits < 19 && slot_for(mean_of(int64_t(1) << bits)) > cap) ++bits;
-  const int64_t slot = slot_for(mean_of(int64_t(1) << bits));
-  const int db2 = std::min(9, bits / 2), db1 = bits - db2;
+  while (bits < 19 && sizing::slot_rows(mean_of(int64_t(1) << bits)) > cap) ++bits;
+  const int64_t slot = sizing::slot_rows(mean_of(int64_t(1) << bits));
+  const auto [db1, db2] = sizing::digit_split(bits);
   if (slot > cap || bits > hr || !hip::radix_slot_eligible(n, 1, db1, db2)) return nullptr;
   CYLON_PHASE("sort.radix_msd", ex.device);
   const int64_t nb1 = int64_t(1) << db1, nparts = int64_t(1) << bits, tail = hip::radix_slot_tile_rows();
   // first pass into (XCD, bucket) slots when the second pass's segment table holds 8 x 2^db1 of them,
   // else exact (2B keys: 19 bits = 10 + 9)
   const bool slot1 = hip::radix_slot_first_pass_ok(db1);
-  const int64_t s1 = slot1 ? slot_for(mean_of(8 * nb1)) : 0;
+  const int64_t s1 = slot1 ? sizing::slot_rows(mean_of(8 * nb1)) : 0;
   at::Tensor ovf = at::zeros({1}, ex.opts(at::kInt));
   unsigned int *ov = reinterpret_cast<unsigned int *>(ovf.data_ptr<int>());
   at::Tensor mid = ex.empty_i64(slot1 ? 8 * nb1 * s1 + tail : n), cnt1 = slot1 ? ex.empty_i64(8 * nb1) : at::Tensor();

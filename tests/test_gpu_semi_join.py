@@ -1,5 +1,5 @@
 """Left semi / anti joins on the MI355X: the LDS key-set kernels (kernels/semi_join.hip k_sj_build /
-k_sj_probe) behind ops/join.cpp semi_join_local.  Every case is compared, WITHOUT sorting (local
+k_sj_probe) behind ops/join_semi.cpp semi_join_local.  Every case is compared, WITHOUT sorting (local
 joins keep left's row order), with a Python-set oracle that does not use the engine
 (semi_join_utils) and with the same call on the CPU context.
 

@@ -1,4 +1,4 @@
-"""Left semi / anti joins on CPU contexts (ops/join.cpp semi_join_local; kernels/cpu_semi.cpp is the
+"""Left semi / anti joins on CPU contexts (ops/join_semi.cpp semi_join_local; kernels/cpu_semi.cpp is the
 twin of kernels/semi_join.hip): every key kind, payload kind, degenerate input and public surface,
 against a Python-set oracle that does not use the engine (semi_join_utils).  Local results are
 compared WITHOUT sorting: they keep the left table's row order (docs/semantics.md)."""
