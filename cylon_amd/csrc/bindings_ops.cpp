@@ -369,6 +369,63 @@ void register_extended_ops(py::module &m) {
       py::arg("table"), py::arg("partition_cols"), py::arg("order_cols"), py::arg("ascending"), py::arg("funcs"),
       py::arg("cols"), py::arg("args"), py::arg("names"), py::arg("preceding"), py::arg("following"),
       py::arg("min_periods"), rel);
+  // as-of join: tolerance = None, an int (integer / temporal `on`) or a float (float `on`)
+  auto asof_options = [](int direction, bool allow_exact, const py::object &tolerance, const std::string &left_prefix,
+                         const std::string &right_prefix) {
+    AsofOptions o;
+    o.direction = direction;
+    o.allow_exact_matches = allow_exact;
+    if (!tolerance.is_none()) {
+      CYLON_CHECK(!py::isinstance<py::bool_>(tolerance) &&
+                      (py::isinstance<py::int_>(tolerance) || py::isinstance<py::float_>(tolerance)),
+                  Code::Invalid, "asof join: tolerance must be an int or a float");
+      o.has_tolerance = true;
+      o.tolerance_is_float = py::isinstance<py::float_>(tolerance);
+      if (o.tolerance_is_float) o.tolerance_f = tolerance.cast<double>();
+      else o.tolerance_i = tolerance.cast<int64_t>();
+    }
+    o.left_prefix = left_prefix;
+    o.right_prefix = right_prefix;
+    return o;
+  };
+  m.def(
+      "asof_join",
+      [asof_options](const TablePtr &l, const TablePtr &r, int left_on, int right_on, const std::vector<int> &left_by,
+                     const std::vector<int> &right_by, int direction, bool allow_exact, const py::object &tolerance,
+                     const std::string &left_prefix, const std::string &right_prefix, int64_t carry_step_tiles) {
+        const AsofOptions o = asof_options(direction, allow_exact, tolerance, left_prefix, right_prefix);
+        py::gil_scoped_release nogil;
+        return ops::AsofJoin(l, r, left_on, right_on, left_by, right_by, o, carry_step_tiles);
+      },
+      py::arg("left"), py::arg("right"), py::arg("left_on"), py::arg("right_on"), py::arg("left_by"),
+      py::arg("right_by"), py::arg("direction") = 0, py::arg("allow_exact_matches") = true,
+      py::arg("tolerance") = py::none(), py::arg("left_prefix") = "", py::arg("right_prefix") = "",
+      py::arg("carry_step_tiles") = 0);
+  m.def(
+      "distributed_asof_join",
+      [asof_options](const TablePtr &l, const TablePtr &r, int left_on, int right_on, const std::vector<int> &left_by,
+                     const std::vector<int> &right_by, int direction, bool allow_exact, const py::object &tolerance,
+                     const std::string &left_prefix, const std::string &right_prefix) {
+        const AsofOptions o = asof_options(direction, allow_exact, tolerance, left_prefix, right_prefix);
+        py::gil_scoped_release nogil;
+        return ops::DistributedAsofJoin(l, r, left_on, right_on, left_by, right_by, o);
+      },
+      py::arg("left"), py::arg("right"), py::arg("left_on"), py::arg("right_on"), py::arg("left_by"),
+      py::arg("right_by"), py::arg("direction") = 0, py::arg("allow_exact_matches") = true,
+      py::arg("tolerance") = py::none(), py::arg("left_prefix") = "", py::arg("right_prefix") = "");
+  // the right row of every left row (-1: none): AsofJoin is left ++ GatherNullable(right, that, true)
+  m.def(
+      "asof_join_indices",
+      [asof_options](const TablePtr &l, const TablePtr &r, int left_on, int right_on, const std::vector<int> &left_by,
+                     const std::vector<int> &right_by, int direction, bool allow_exact, const py::object &tolerance,
+                     int64_t carry_step_tiles) {
+        const AsofOptions o = asof_options(direction, allow_exact, tolerance, "", "");
+        py::gil_scoped_release nogil;
+        return ops::AsofJoinIndices(l, r, left_on, right_on, left_by, right_by, o, carry_step_tiles);
+      },
+      py::arg("left"), py::arg("right"), py::arg("left_on"), py::arg("right_on"), py::arg("left_by"),
+      py::arg("right_by"), py::arg("direction") = 0, py::arg("allow_exact_matches") = true,
+      py::arg("tolerance") = py::none(), py::arg("carry_step_tiles") = 0);
   // rows per tile of the window scans and tiles per step of their carry scan (kernels/window.hip); the
   // CPU twin is one sequential loop and reports the same numbers
   m.def("window_tile_rows", []() { return hip::window_tile_rows(); });

@@ -207,6 +207,30 @@ CYLON_CAPI int cylon_window_frames(const char *id, const int32_t *partition_cols
   });
 }
 
+CYLON_CAPI int cylon_asof_join(const char *left_id, const char *right_id, int left_on, int right_on,
+                               const int32_t *left_by, const int32_t *right_by, int nby, int direction, int allow_exact,
+                               int has_tolerance, int64_t tolerance_i, double tolerance_f, const char *left_prefix,
+                               const char *right_prefix, const char *dest, int distributed) {
+  return guard([&] {
+    if (nby < 0 || (nby > 0 && (left_by == nullptr || right_by == nullptr)))
+      return status(Status(Code::Invalid, "asof join: `by` columns"));
+    AsofOptions o;
+    o.direction = direction;
+    o.allow_exact_matches = allow_exact != 0;
+    o.has_tolerance = has_tolerance != 0;
+    o.tolerance_i = tolerance_i;
+    o.tolerance_f = tolerance_f;
+    if (o.has_tolerance) {  // the `on` column's type says which of the two tolerances counts
+      const TablePtr l = GetTable(left_id);
+      o.tolerance_is_float = left_on >= 0 && left_on < l->Columns() && l->column(left_on).type.kind() == ValueKind::FLOAT;
+    }
+    o.left_prefix = left_prefix ? left_prefix : "";
+    o.right_prefix = right_prefix ? right_prefix : "";
+    return status(AsofJoinTables(left_id, right_id, left_on, right_on, std::vector<int32_t>(left_by, left_by + nby),
+                                 std::vector<int32_t>(right_by, right_by + nby), o, dest, distributed != 0));
+  });
+}
+
 CYLON_CAPI int cylon_project(const char *id, const int32_t *cols, int n, const char *dest) {
   return guard([&] {
     TablePtr out;

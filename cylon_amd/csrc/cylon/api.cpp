@@ -104,6 +104,22 @@ Status DistributedWindow(const TablePtr &t, const std::vector<int32_t> &partitio
                                  std::vector<int>(order_cols.begin(), order_cols.end()), dirs, specs);
   });
 }
+Status AsofJoin(const TablePtr &left, const TablePtr &right, int left_on, int right_on,
+                const std::vector<int32_t> &left_by, const std::vector<int32_t> &right_by, const AsofOptions &options,
+                TablePtr &out) {
+  return guard([&] {
+    out = ops::AsofJoin(left, right, left_on, right_on, std::vector<int>(left_by.begin(), left_by.end()),
+                        std::vector<int>(right_by.begin(), right_by.end()), options);
+  });
+}
+Status DistributedAsofJoin(const TablePtr &left, const TablePtr &right, int left_on, int right_on,
+                           const std::vector<int32_t> &left_by, const std::vector<int32_t> &right_by,
+                           const AsofOptions &options, TablePtr &out) {
+  return guard([&] {
+    out = ops::DistributedAsofJoin(left, right, left_on, right_on, std::vector<int>(left_by.begin(), left_by.end()),
+                                   std::vector<int>(right_by.begin(), right_by.end()), options);
+  });
+}
 Status Shuffle(const TablePtr &t, const std::vector<int> &cols, TablePtr &out) {
   return guard([&] { out = ops::Shuffle(t, cols); });
 }
@@ -302,6 +318,16 @@ Status WindowTable(const std::string &id, const std::vector<int32_t> &partition_
     const std::vector<int> order(order_cols.begin(), order_cols.end());
     PutTable(dest, distributed ? ops::DistributedWindow(GetTable(id), part, order, dirs, specs)
                                : ops::Window(GetTable(id), part, order, dirs, specs));
+  });
+}
+Status AsofJoinTables(const std::string &left_id, const std::string &right_id, int left_on, int right_on,
+                      const std::vector<int32_t> &left_by, const std::vector<int32_t> &right_by,
+                      const AsofOptions &options, const std::string &dest_id, bool distributed) {
+  return guard([&] {
+    const std::vector<int> lby(left_by.begin(), left_by.end()), rby(right_by.begin(), right_by.end());
+    const TablePtr l = GetTable(left_id), r = GetTable(right_id);
+    PutTable(dest_id, distributed ? ops::DistributedAsofJoin(l, r, left_on, right_on, lby, rby, options)
+                                  : ops::AsofJoin(l, r, left_on, right_on, lby, rby, options));
   });
 }
 

@@ -67,6 +67,13 @@ Status Window(const TablePtr &t, const std::vector<int32_t> &partition_cols, con
 Status DistributedWindow(const TablePtr &t, const std::vector<int32_t> &partition_cols,
                          const std::vector<int32_t> &order_cols, const std::vector<bool> &dirs,
                          const std::vector<WindowSpec> &specs, TablePtr &out);
+// as-of join (docs/semantics.md "As-of join"): left's rows plus the nearest right row of the same group
+Status AsofJoin(const TablePtr &left, const TablePtr &right, int left_on, int right_on,
+                const std::vector<int32_t> &left_by, const std::vector<int32_t> &right_by, const AsofOptions &options,
+                TablePtr &out);
+Status DistributedAsofJoin(const TablePtr &left, const TablePtr &right, int left_on, int right_on,
+                           const std::vector<int32_t> &left_by, const std::vector<int32_t> &right_by,
+                           const AsofOptions &options, TablePtr &out);
 Status Shuffle(const TablePtr &t, const std::vector<int> &hash_cols, TablePtr &out);
 Status HashPartition(const TablePtr &t, const std::vector<int> &hash_cols, int num_partitions,
                      std::map<int, TablePtr> *out);
@@ -160,6 +167,9 @@ Status TopKTable(const std::string &id, int col, int64_t k, const std::string &d
 Status WindowTable(const std::string &id, const std::vector<int32_t> &partition_cols,
                    const std::vector<int32_t> &order_cols, const std::vector<bool> &dirs,
                    const std::vector<WindowSpec> &specs, const std::string &dest, bool distributed);
+Status AsofJoinTables(const std::string &left_id, const std::string &right_id, int left_on, int right_on,
+                      const std::vector<int32_t> &left_by, const std::vector<int32_t> &right_by,
+                      const AsofOptions &options, const std::string &dest_id, bool distributed);
 int64_t RowCount(const std::string &id);
 int32_t ColumnCount(const std::string &id);
 std::vector<std::string> ColumnNames(const std::string &id);

@@ -569,3 +569,30 @@ void rolling_combine(const ColView &col, const int64_t *perm, const int64_t *phe
                      int func, bool mean, int64_t preceding, int64_t following, int64_t min_periods,
                      const uint64_t *fwd, const uint32_t *fwd_cnt, const uint64_t *bwd, const uint32_t *bwd_cnt,
                      uint8_t *out, uint8_t *out_valid, void *stream);
+
+/* asof.hip (CPU twin cpu_asof.cpp): the as-of join's scan over the merged order of both sides' key
+   rows (docs/semantics.md "As-of join").  perm = the stable sort of the n concatenated key rows, the
+   first nfirst of them from one side; sorted position i holds a right row where
+   (perm[i] < nfirst) == right_first.  reverse = false: scan position k is sorted position k and
+   restarts = the partition heads (bit 0); reverse = true: it is sorted position n - 1 - k and
+   restarts = window_rev_flags' output.  The scan is the segmented running maximum of "scan position
+   + 1 for a right row whose `on` is neither null nor NaN, else 0", in three launches over tiles of
+   window_tile_rows() positions:
+     asof_tile     reads `on` (the concatenated column) at perm, writes code[k] (asof_common.hpp) in
+                   scan order and one (flag, aggregate) pair per tile.
+     window_carry  (words 1, func 3): each tile's carry-in.
+     asof_apply    re-scans each tile; every left position writes match[left row] = the right row at
+                   the carried scan position, -1 for none or for a null / NaN `on`.
+   asof_pick: match[i] = asof_pick_one of the backward candidate back[i] and the forward one fwd[i]
+   (fwd == nullptr: none; back may be match) -- the nearer one, the backward one on equal distances,
+   -1 when farther than the tolerance (tolerance_i for an integer or temporal `on`, tolerance_f for a
+   float one).  matched != nullptr: asof_apply / asof_pick add the left rows they gave a match to it.
+   The CPU twin is the definition: its asof_tile only writes the codes, its asof_apply is one
+   sequential loop over the positions. */
+void asof_tile(const ColView &on, const int64_t *perm, const uint8_t *restarts, int64_t n, int64_t nfirst,
+               bool right_first, bool reverse, uint8_t *code, int64_t *tile_agg, uint8_t *tile_flag, void *stream);
+void asof_apply(const int64_t *perm, const uint8_t *restarts, const uint8_t *code, int64_t n, int64_t nfirst,
+                bool right_first, bool reverse, const int64_t *carry, int64_t *match, int64_t *matched, void *stream);
+void asof_pick(const ColView &left_on, const ColView &right_on, int64_t nl, const int64_t *back, const int64_t *fwd,
+               bool has_tolerance, int64_t tolerance_i, double tolerance_f, int64_t *match, int64_t *matched,
+               void *stream);

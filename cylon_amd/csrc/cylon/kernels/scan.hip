@@ -320,6 +320,7 @@ void mark_indices(const int64_t *idx, int64_t m, uint8_t *flags, void *stream) {
 // this file's code object is loaded at context creation (preload_device_code), not on first use
 void preload_scan() { preload_code(reinterpret_cast<const void *>(&k_block_sums)); }
 
+void preload_asof();
 void preload_bitmap();
 void preload_copy();
 void preload_delay();
@@ -347,6 +348,7 @@ void preload_window();
 // launch from it: inside a pipelined join that stalled the host for up to 40 ms while the posted
 // transfers ran with nothing to overlap, profiles/r05/first_step_overlap.txt)
 void preload_device_code() {
+  preload_asof();
   preload_bitmap();
   preload_copy();
   preload_delay();

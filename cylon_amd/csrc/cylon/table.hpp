@@ -117,6 +117,22 @@ struct WindowSpec {
   int64_t min_periods = 1;
 };
 
+// As-of join (docs/semantics.md "As-of join"): every left row with the nearest right row of its group
+// at or before it (BACKWARD), at or after it (FORWARD), or the nearer of the two (NEAREST).
+enum AsofDirection : int { ASOF_BACKWARD = 0, ASOF_FORWARD = 1, ASOF_NEAREST = 2 };
+
+struct AsofOptions {
+  int direction = ASOF_BACKWARD;  // an AsofDirection; any other number is Invalid
+  bool allow_exact_matches = true;
+  // a match farther away than the tolerance (>= 0) is dropped: tolerance_i in the column's unit for an
+  // integer or temporal `on` (tolerance_is_float = false), tolerance_f for a float `on` (true)
+  bool has_tolerance = false;
+  bool tolerance_is_float = false;
+  int64_t tolerance_i = 0;
+  double tolerance_f = 0;
+  std::string left_prefix, right_prefix;
+};
+
 namespace ops {
 
 // ---- plumbing -------------------------------------------------------------
@@ -226,6 +242,21 @@ TablePtr Window(const TablePtr &t, const std::vector<int> &partition_cols, const
 TablePtr DistributedWindow(const TablePtr &t, const std::vector<int> &partition_cols,
                            const std::vector<int> &order_cols, const std::vector<bool> &ascending,
                            const std::vector<WindowSpec> &specs);
+// As-of join (ops/asof.cpp): left's rows in left's row order, followed by right's columns gathered
+// from the match of every left row (null where there is none); names get the prefixes as Join's do.
+// Neither input needs to be sorted.  AsofJoinIndices: the right row of every left row, -1 for none.
+// carry_step_tiles > 0 (tests only) lowers the tiles one step of the carry scan covers.
+// DistributedAsofJoin: shuffle both sides by their `by` columns (at least one), then AsofJoin on every
+// rank; the output row order is unspecified.
+at::Tensor AsofJoinIndices(const TablePtr &left, const TablePtr &right, int left_on, int right_on,
+                           const std::vector<int> &left_by, const std::vector<int> &right_by,
+                           const AsofOptions &options, int64_t carry_step_tiles = 0);
+TablePtr AsofJoin(const TablePtr &left, const TablePtr &right, int left_on, int right_on,
+                  const std::vector<int> &left_by, const std::vector<int> &right_by, const AsofOptions &options,
+                  int64_t carry_step_tiles = 0);
+TablePtr DistributedAsofJoin(const TablePtr &left, const TablePtr &right, int left_on, int right_on,
+                             const std::vector<int> &left_by, const std::vector<int> &right_by,
+                             const AsofOptions &options);
 
 }  // namespace ops
 }  // namespace cylon

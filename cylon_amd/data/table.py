@@ -469,6 +469,66 @@ class Table(PandasOpsMixin):
                 self._t, *self._window_frame_args(partition_by, order_by, ascending, funcs)))
         return self._wrap(C.distributed_window(self._t, *self._window_args(partition_by, order_by, ascending, funcs)))
 
+    _ASOF_DIRECTIONS = {"backward": 0, "forward": 1, "nearest": 2}
+
+    def _asof_column(self, c) -> int:
+        """a name -> its index; an integer goes to the engine as it is (out of range: Code::Invalid)"""
+        if isinstance(c, (int, np.integer)) and not isinstance(c, bool):
+            return int(c)
+        idx = self._t.column_index(str(c))
+        if idx < 0:
+            raise KeyError(f"column '{c}' not found in {self.column_names}")
+        return idx
+
+    def _asof_args(self, table: "Table", on, left_on, right_on, by, left_by, right_by, direction, allow_exact_matches,
+                   tolerance):
+        if on is not None:
+            left_on = right_on = on
+        if left_on is None or right_on is None or isinstance(left_on, (list, tuple)) or isinstance(right_on, (list, tuple)):
+            raise ValueError("asof_join needs one `on` column: pass on=, or left_on= and right_on=")
+        if by is not None:
+            left_by = right_by = by
+        as_list = lambda b: [] if b is None else (list(b) if isinstance(b, (list, tuple)) else [b])
+        lby, rby = as_list(left_by), as_list(right_by)
+        if len(lby) != len(rby):
+            raise ValueError(f"asof_join: {len(lby)} left and {len(rby)} right `by` columns")
+        if isinstance(direction, str):
+            if direction.lower() not in self._ASOF_DIRECTIONS:
+                raise ValueError(f"unknown asof direction {direction!r}; one of {sorted(self._ASOF_DIRECTIONS)}")
+            direction = self._ASOF_DIRECTIONS[direction.lower()]
+        if tolerance is not None:
+            if isinstance(tolerance, (bool, np.bool_)) or not isinstance(tolerance, (int, float, np.integer, np.floating)):
+                raise ValueError(f"asof_join: tolerance must be an int or a float, got {tolerance!r}")
+            tolerance = int(tolerance) if isinstance(tolerance, (int, np.integer)) else float(tolerance)
+            if isinstance(tolerance, int) and not -(1 << 63) <= tolerance < (1 << 63):
+                raise ValueError(f"asof_join: tolerance {tolerance} does not fit 64 bits")
+        return (self._asof_column(left_on), table._asof_column(right_on), [self._asof_column(c) for c in lby],
+                [table._asof_column(c) for c in rby], int(direction), bool(allow_exact_matches), tolerance)
+
+    def asof_join(self, table: "Table", on=None, left_on=None, right_on=None, by=None, left_by=None, right_by=None,
+                  direction: str = "backward", allow_exact_matches: bool = True, tolerance=None,
+                  left_prefix: str = "", right_prefix: str = "") -> "Table":
+        """As-of join (pandas.merge_asof, SQL ASOF JOIN): this table's rows in its row order, followed by the
+        columns of the nearest row of `table` whose `by` columns equal the row's own -- direction
+        "backward": the last one with right_on <= left_on, "forward": the first one with right_on >=
+        left_on, "nearest": the nearer of the two, the backward one on equal distances.
+        allow_exact_matches=False makes the comparisons strict; a match farther away than `tolerance` (an
+        int in the column's unit for an integer or temporal `on`, a float for a float `on`) is dropped.
+        Right columns are null where there is no match.  Neither table needs to be sorted; a null or NaN
+        `on` never matches (docs/semantics.md "As-of join")."""
+        args = self._asof_args(table, on, left_on, right_on, by, left_by, right_by, direction, allow_exact_matches,
+                               tolerance)
+        return self._wrap(C.asof_join(self._t, table._t, *args, left_prefix, right_prefix))
+
+    def distributed_asof_join(self, table: "Table", on=None, left_on=None, right_on=None, by=None, left_by=None,
+                              right_by=None, direction: str = "backward", allow_exact_matches: bool = True,
+                              tolerance=None, left_prefix: str = "", right_prefix: str = "") -> "Table":
+        """asof_join() after a shuffle of both tables by their `by` columns (at least one when the world is
+        larger than 1); the output row order is unspecified."""
+        args = self._asof_args(table, on, left_on, right_on, by, left_by, right_by, direction, allow_exact_matches,
+                               tolerance)
+        return self._wrap(C.distributed_asof_join(self._t, table._t, *args, left_prefix, right_prefix))
+
     def shuffle(self, hash_columns: List = None) -> "Table":
         return self._wrap(C.shuffle(self._t, self._resolve_columns(hash_columns)))
 

@@ -413,6 +413,22 @@ class DataFrame(object):
             return DataFrame(self._table.window(partition_by, order_by, ascending, funcs))
         return DataFrame(self._change_context(env)._table.distributed_window(partition_by, order_by, ascending, funcs))
 
+    def merge_asof(self, right: "DataFrame", on=None, left_on=None, right_on=None, by=None, left_by=None,
+                   right_by=None, suffixes=("_x", "_y"), tolerance=None, allow_exact_matches: bool = True,
+                   direction: str = "backward", env: CylonEnv = None) -> "DataFrame":
+        """pandas.merge_asof through Table.asof_join: every row of this frame with the nearest row of `right`
+        by `on` within the `by` groups.  Neither frame needs to be sorted.  As in merge(), the suffixes
+        are applied as prefixes to every column of their side.  With an env of more than one rank both
+        frames are first shuffled by their `by` columns."""
+        kw = dict(on=on, left_on=left_on, right_on=right_on, by=by, left_by=left_by, right_by=right_by,
+                  direction=direction, allow_exact_matches=allow_exact_matches, tolerance=tolerance,
+                  left_prefix=suffixes[0], right_prefix=suffixes[1])
+        if env is None or env.world_size <= 1:
+            return DataFrame(self._table.asof_join(right._table, **kw))
+        self._change_context(env)
+        right._change_context(env)
+        return DataFrame(self._table.distributed_asof_join(right._table, **kw))
+
     def groupby(self, by, agg: dict, algorithm: str = "hash", env: CylonEnv = None) -> "DataFrame":
         if env is None:
             return DataFrame(self._table.local_groupby(by, agg, algorithm))

@@ -68,6 +68,17 @@ int cylon_window_frames(const char *table_id, const int32_t *partition_columns, 
                         const int32_t *spec_columns, const int64_t *spec_args, const int64_t *preceding,
                         const int64_t *following, const int64_t *min_periods, const char *const *names, int nspecs,
                         int distributed, const char *dest_id);
+/* as-of join: every row of the left table, in its row order, with the columns of the nearest right row
+   whose `by` columns equal its own (nby may be 0) -- direction 0 BACKWARD: the last right_on <=
+   left_on, 1 FORWARD: the first right_on >= left_on, 2 NEAREST: the nearer of the two, the backward
+   one on equal distances; allow_exact == 0 makes the comparisons strict.  has_tolerance != 0 drops
+   matches farther away than tolerance_i (integer or temporal `on`, in the column's unit) or
+   tolerance_f (float `on`); the other one is ignored.  Right columns are null where there is no match;
+   names get the prefixes (NULL: none).  distributed != 0 needs a `by` column at world sizes > 1. */
+int cylon_asof_join(const char *left_id, const char *right_id, int left_on, int right_on, const int32_t *left_by,
+                    const int32_t *right_by, int nby, int direction, int allow_exact, int has_tolerance,
+                    int64_t tolerance_i, double tolerance_f, const char *left_prefix, const char *right_prefix,
+                    const char *dest_id, int distributed);
 int cylon_project(const char *table_id, const int32_t *columns, int ncolumns, const char *dest_id);
 
 int cylon_merge(const char *const *table_ids, int ntables, const char *dest_id);

@@ -72,6 +72,16 @@ def distributed_window(t: Table, partition_by=None, order_by=None, ascending: Un
     return t.distributed_window(partition_by, order_by, ascending, funcs)
 
 
+def asof_join(left: Table, right: Table, **kwargs) -> Table:
+    """Table.asof_join: on= | left_on=, right_on=; by= | left_by=, right_by=; direction, allow_exact_matches,
+    tolerance, left_prefix, right_prefix."""
+    return left.asof_join(right, **kwargs)
+
+
+def distributed_asof_join(left: Table, right: Table, **kwargs) -> Table:
+    return left.distributed_asof_join(right, **kwargs)
+
+
 def shuffle(t: Table, hash_columns: List = None) -> Table:
     return t.shuffle(hash_columns)
 
@@ -107,5 +117,5 @@ def merge(tables: Sequence[Table]) -> Table:
 
 __all__ = ["join", "distributed_join", "union", "subtract", "intersect", "distributed_union",
            "distributed_subtract", "distributed_intersect", "sort", "distributed_sort", "topk",
-           "distributed_topk", "window", "distributed_window", "shuffle",
+           "distributed_topk", "window", "distributed_window", "asof_join", "distributed_asof_join", "shuffle",
            "hash_partition", "unique", "distributed_unique", "groupby", "local_groupby", "project", "merge"]
