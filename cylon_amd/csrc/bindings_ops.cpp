@@ -369,6 +369,61 @@ void register_extended_ops(py::module &m) {
       py::arg("table"), py::arg("partition_cols"), py::arg("order_cols"), py::arg("ascending"), py::arg("funcs"),
       py::arg("cols"), py::arg("args"), py::arg("names"), py::arg("preceding"), py::arg("following"),
       py::arg("min_periods"), rel);
+  // the same with RANGE frames too (functions 0 .. 18): preceding / following are then distances in the
+  // order column's values, INT64_MAX meaning unbounded; where offset_is_float[i], a side that is not
+  // unbounded reads preceding_f[i] / following_f[i] instead
+  auto range_specs = [](const std::vector<int> &funcs, const std::vector<int> &cols, const std::vector<int64_t> &args,
+                        const std::vector<std::string> &names, const std::vector<int64_t> &preceding,
+                        const std::vector<int64_t> &following, const std::vector<double> &preceding_f,
+                        const std::vector<double> &following_f, const std::vector<bool> &offset_is_float,
+                        const std::vector<int64_t> &min_periods) {
+    const size_t k = funcs.size();
+    CYLON_CHECK(cols.size() == k && args.size() == k && names.size() == k && preceding.size() == k &&
+                    following.size() == k && preceding_f.size() == k && following_f.size() == k &&
+                    offset_is_float.size() == k && min_periods.size() == k,
+                Code::Invalid, "window spec lists differ in length");
+    std::vector<WindowSpec> specs;
+    for (size_t i = 0; i < k; ++i) {
+      CYLON_CHECK(funcs[i] >= WIN_ROW_NUMBER && funcs[i] <= WIN_RANGE_MAX, Code::Invalid,
+                  "window function " << funcs[i]);
+      specs.push_back({static_cast<WindowFunc>(funcs[i]), cols[i], args[i], names[i], preceding[i], following[i],
+                       min_periods[i], preceding_f[i], following_f[i], offset_is_float[i]});
+    }
+    return specs;
+  };
+  m.def(
+      "window_range_frames",
+      [range_specs](const TablePtr &t, const std::vector<int> &part, const std::vector<int> &order,
+                    const std::vector<bool> &asc, const std::vector<int> &funcs, const std::vector<int> &cols,
+                    const std::vector<int64_t> &args, const std::vector<std::string> &names,
+                    const std::vector<int64_t> &preceding, const std::vector<int64_t> &following,
+                    const std::vector<double> &preceding_f, const std::vector<double> &following_f,
+                    const std::vector<bool> &offset_is_float, const std::vector<int64_t> &min_periods,
+                    int64_t carry_step_tiles) {
+        return ops::Window(t, part, order, asc,
+                           range_specs(funcs, cols, args, names, preceding, following, preceding_f, following_f,
+                                       offset_is_float, min_periods),
+                           carry_step_tiles);
+      },
+      py::arg("table"), py::arg("partition_cols"), py::arg("order_cols"), py::arg("ascending"), py::arg("funcs"),
+      py::arg("cols"), py::arg("args"), py::arg("names"), py::arg("preceding"), py::arg("following"),
+      py::arg("preceding_f"), py::arg("following_f"), py::arg("offset_is_float"), py::arg("min_periods"),
+      py::arg("carry_step_tiles") = 0, rel);
+  m.def(
+      "distributed_window_range_frames",
+      [range_specs](const TablePtr &t, const std::vector<int> &part, const std::vector<int> &order,
+                    const std::vector<bool> &asc, const std::vector<int> &funcs, const std::vector<int> &cols,
+                    const std::vector<int64_t> &args, const std::vector<std::string> &names,
+                    const std::vector<int64_t> &preceding, const std::vector<int64_t> &following,
+                    const std::vector<double> &preceding_f, const std::vector<double> &following_f,
+                    const std::vector<bool> &offset_is_float, const std::vector<int64_t> &min_periods) {
+        return ops::DistributedWindow(t, part, order, asc,
+                                      range_specs(funcs, cols, args, names, preceding, following, preceding_f,
+                                                  following_f, offset_is_float, min_periods));
+      },
+      py::arg("table"), py::arg("partition_cols"), py::arg("order_cols"), py::arg("ascending"), py::arg("funcs"),
+      py::arg("cols"), py::arg("args"), py::arg("names"), py::arg("preceding"), py::arg("following"),
+      py::arg("preceding_f"), py::arg("following_f"), py::arg("offset_is_float"), py::arg("min_periods"), rel);
   // as-of join: tolerance = None, an int (integer / temporal `on`) or a float (float `on`)
   auto asof_options = [](int direction, bool allow_exact, const py::object &tolerance, const std::string &left_prefix,
                          const std::string &right_prefix) {
@@ -432,6 +487,10 @@ void register_extended_ops(py::module &m) {
   m.def("window_carry_tiles", []() { return hip::window_carry_tiles(); });
   // the widest frame (preceding + following + 1) that the one-launch LDS kernel of kernels/rolling.hip takes
   m.def("window_frame_lds_rows", []() { return hip::window_frame_lds_rows(); });
+  // RANGE frames (kernels/frame_range.hip): entries per block of the scan pyramid, and the keys staged on
+  // either side of a tile by the bounds search (a bound further away is found in global memory)
+  m.def("window_range_radix", []() { return hip::window_range_radix(); });
+  m.def("window_range_halo", []() { return hip::window_range_halo(); });
   // the radix partitions' sizing rules (ops/radix_sizing.hpp): partition bits of `rows` build rows against
   // an LDS capacity, and the slot-mode rows per partition of `rows` rows in `nparts` partitions
   m.def("radix_partition_bits", [](int64_t rows, int64_t cap) { return ops::sizing::partition_bits(rows, cap); });

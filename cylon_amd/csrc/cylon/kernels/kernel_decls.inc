@@ -570,6 +570,41 @@ void rolling_combine(const ColView &col, const int64_t *perm, const int64_t *phe
                      const uint64_t *fwd, const uint32_t *fwd_cnt, const uint64_t *bwd, const uint32_t *bwd_cnt,
                      uint8_t *out, uint8_t *out_valid, void *stream);
 
+/* frame_range.hip (CPU twin cpu_frame_range.cpp): aggregates over the RANGE frame of sorted position
+   i, the positions j of i's partition whose order key lies within `preceding` below and `following`
+   above i's (docs/semantics.md "Framed aggregates", RANGE).  Shared rules: frame_range_common.hpp.
+     frame_range_keys     from the order column's dense values (window_tile's gather) the search key of
+                          every sorted position: keys[i] = a 64-bit image that never decreases along a
+                          partition's numbers (flipped for a descending column), cls[i] = 0 number,
+                          1 NaN, 2 null (keys 0).
+     frame_range_bounds   lo[i] / hi[i] = the first / last sorted position of i's frame, by binary
+                          search over (cls, keys) inside [phead, tail] (rtail as rolling_lds takes it).
+                          A side's mode: 0 unbounded (the partition's head / tail), 1 an integer
+                          distance (integer keys), 2 a float64 distance (float keys).
+     frame_range_pyramid  the radix-window_range_radix() two-sided scan pyramid of one (column, func):
+                          per level P (scan from the 8-block's start to the entry) and S (from the entry
+                          to the block's end), and E = one total per block = the next level's entries.
+                          P, S: fr_ps_slots(n) words, E: fr_e_slots(n) words (frame_range_common.hpp).
+     frame_range_apply    out[perm[i]] = the aggregate of [lo[i], hi[i]] read off the pyramid, at most two
+                          words per level; the non-null count m = hi - lo + 1, or, for a column with
+                          nulls, read off the count pyramid (func 4) cP / cS / cE.  func, mean,
+                          min_periods, out and out_valid as rolling_combine's.  func 4 needs no
+                          pyramid of a column without nulls.
+   n < 2^32. */
+int64_t window_range_radix();
+int64_t window_range_halo();
+void frame_range_keys(const ColView &order_col, const uint64_t *dense, const uint8_t *dense_valid, int64_t n,
+                      bool descending, uint64_t *keys, uint8_t *cls, void *stream);
+void frame_range_bounds(const uint64_t *keys, const uint8_t *cls, const int64_t *phead, const int64_t *rtail,
+                        int64_t n, bool float_keys, bool descending, int pre_mode, uint64_t pre_i, double pre_f,
+                        int fol_mode, uint64_t fol_i, double fol_f, uint32_t *lo, uint32_t *hi, void *stream);
+void frame_range_pyramid(const ColView &col, int64_t n, int func, const uint64_t *dense, const uint8_t *dense_valid,
+                         uint64_t *P, uint64_t *S, uint64_t *E, void *stream);
+void frame_range_apply(const ColView &col, const int64_t *perm, int64_t n, int func, bool mean, int64_t min_periods,
+                       const uint64_t *dense, const uint8_t *dense_valid, const uint32_t *lo, const uint32_t *hi,
+                       const uint64_t *P, const uint64_t *S, const uint64_t *E, const uint64_t *cP,
+                       const uint64_t *cS, const uint64_t *cE, uint8_t *out, uint8_t *out_valid, void *stream);
+
 /* asof.hip (CPU twin cpu_asof.cpp): the as-of join's scan over the merged order of both sides' key
    rows (docs/semantics.md "As-of join").  perm = the stable sort of the n concatenated key rows, the
    first nfirst of them from one side; sorted position i holds a right row where

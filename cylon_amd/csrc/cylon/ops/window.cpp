@@ -13,9 +13,17 @@
 // frame of at most window_frame_lds_rows() rows is one launch of kernels/rolling.hip (rolling_lds);
 // a wider one scans forwards and over the reversed order (rolling_tile / window_carry /
 // rolling_scan) and combines the two (rolling_combine).
+//
+// A RANGE spec (a frame over the one order column's values) shares all of that too.  The order column
+// is gathered like a value column and turned into search keys once per call; every distinct
+// (preceding, following) gets one bounds search (lo / hi per sorted position), every (column, operator)
+// one scan pyramid, and a spec is then one query launch of kernels/frame_range.hip.
 #include <algorithm>
 #include <map>
 #include <set>
+#include <tuple>
+
+#include "../kernels/frame_range_common.hpp"
 
 #include "../trace.hpp"
 #include "util.hpp"
@@ -44,6 +52,11 @@ const char *func_name(WindowFunc f) {
     case WIN_ROLLING_MEAN: return "rolling_mean";
     case WIN_ROLLING_MIN: return "rolling_min";
     case WIN_ROLLING_MAX: return "rolling_max";
+    case WIN_RANGE_COUNT: return "range_count";
+    case WIN_RANGE_SUM: return "range_sum";
+    case WIN_RANGE_MEAN: return "range_mean";
+    case WIN_RANGE_MIN: return "range_min";
+    case WIN_RANGE_MAX: return "range_max";
   }
   CYLON_THROW(Code::Invalid, "window function " << static_cast<int>(f));
 }
@@ -51,6 +64,22 @@ const char *func_name(WindowFunc f) {
 bool is_ranking(WindowFunc f) { return f == WIN_ROW_NUMBER || f == WIN_RANK || f == WIN_DENSE_RANK; }
 bool is_shift(WindowFunc f) { return f == WIN_LAG || f == WIN_LEAD; }
 bool is_rolling(WindowFunc f) { return f >= WIN_ROLLING_COUNT && f <= WIN_ROLLING_MAX; }
+bool is_range(WindowFunc f) { return f >= WIN_RANGE_COUNT && f <= WIN_RANGE_MAX; }
+bool is_framed(WindowFunc f) { return is_rolling(f) || is_range(f); }
+// the ROLLING function whose result rules a RANGE function shares
+WindowFunc rolling_twin(WindowFunc f) {
+  return is_range(f) ? static_cast<WindowFunc>(f - WIN_RANGE_COUNT + WIN_ROLLING_COUNT) : f;
+}
+
+// the order column of a RANGE frame: an integer of any width, a temporal type, float32 or float64
+bool range_order_type(const Column &c) {
+  switch (c.type.type) {
+    case Type::UINT8: case Type::INT8: case Type::UINT16: case Type::INT16: case Type::UINT32: case Type::INT32:
+    case Type::UINT64: case Type::INT64: case Type::FLOAT: case Type::DOUBLE: case Type::DATE32: case Type::DATE64:
+    case Type::TIMESTAMP: case Type::TIME32: case Type::TIME64: case Type::DURATION: return !c.is_var();
+    default: return false;
+  }
+}
 
 bool scan_value(const Column &c) {
   if (c.is_var() || !c.type.is_numeric()) return false;
@@ -66,7 +95,7 @@ Type sum_type(const Column &c) {
 
 // the kernel function and the output type of a value spec
 std::pair<int, DataType> value_plan(const WindowSpec &s, const Column &c) {
-  switch (s.func) {
+  switch (rolling_twin(s.func)) {
     case WIN_CUMCOUNT:
     case WIN_ROLLING_COUNT: return {kCount, DataType(Type::INT64)};
     case WIN_ROLLING_MEAN: return {c.type.kind() == ValueKind::FLOAT ? kSumF : kSumI, DataType(Type::DOUBLE)};
@@ -109,16 +138,35 @@ Checked check(const TablePtr &t, const std::vector<int> &part, const std::vector
         CYLON_CHECK(scan_value(c) && !(s.func == WIN_CUMSUM && c.type.type == Type::HALF_FLOAT), Code::Invalid,
                     "window " << fn << " needs a fixed-width numeric column, got " << c.type.ToString());
       if (is_shift(s.func)) CYLON_CHECK(s.arg >= 0, Code::Invalid, "window " << fn << " offset " << s.arg << " < 0");
-      if (is_rolling(s.func)) {
+      if (is_framed(s.func)) {
+        const WindowFunc rf = rolling_twin(s.func);
         CYLON_CHECK(t->Rows() < (int64_t(1) << 32), Code::Invalid,
                     "window " << fn << " over " << t->Rows() << " rows: framed functions take fewer than 2^32");
-        const bool sum = s.func == WIN_ROLLING_SUM || s.func == WIN_ROLLING_MEAN;
-        CYLON_CHECK(s.func == WIN_ROLLING_COUNT || (scan_value(c) && !(sum && c.type.type == Type::HALF_FLOAT)),
+        const bool sum = rf == WIN_ROLLING_SUM || rf == WIN_ROLLING_MEAN;
+        CYLON_CHECK(rf == WIN_ROLLING_COUNT || (scan_value(c) && !(sum && c.type.type == Type::HALF_FLOAT)),
                     Code::Invalid, "window " << fn << " needs a fixed-width numeric column, got " << c.type.ToString());
         CYLON_CHECK(s.preceding >= 0 && s.following >= 0, Code::Invalid,
                     "window " << fn << " frame of " << s.preceding << " preceding, " << s.following << " following");
-        CYLON_CHECK(s.func == WIN_ROLLING_COUNT || s.min_periods >= 1, Code::Invalid,
+        CYLON_CHECK(rf == WIN_ROLLING_COUNT || s.min_periods >= 1, Code::Invalid,
                     "window " << fn << " min_periods " << s.min_periods << " < 1");
+      }
+      if (is_range(s.func)) {
+        CYLON_CHECK(order.size() == 1, Code::Invalid,
+                    "window " << fn << " needs exactly one order column, got " << order.size());
+        const Column &oc = t->column(order[0]);
+        CYLON_CHECK(range_order_type(oc), Code::Invalid,
+                    "window " << fn << " needs an integer, temporal, float32 or float64 order column, got "
+                              << oc.type.ToString());
+        if (s.offset_is_float) {
+          CYLON_CHECK(oc.type.kind() == ValueKind::FLOAT, Code::Invalid,
+                      "window " << fn << ": a float offset on the " << oc.type.ToString() << " order column");
+          // written so that a NaN fails
+          CYLON_CHECK((s.preceding == kWindowUnbounded || s.preceding_f >= 0) &&
+                          (s.following == kWindowUnbounded || s.following_f >= 0),
+                      Code::Invalid,
+                      "window " << fn << " frame of " << s.preceding_f << " preceding, " << s.following_f
+                                << " following");
+        }
       }
     }
     CYLON_CHECK(taken.insert(name).second, Code::Invalid, "window output column '" << name << "' already exists");
@@ -134,8 +182,8 @@ Column int64_column(const std::string &name, const at::Tensor &v) {
 // A running aggregate is null where its row's value is; a framed one where the frame holds fewer than
 // min_periods values, which a frame of a column without nulls can only do for min_periods > 1.
 bool nullable_result(const WindowSpec &s, const Column &c) {
-  if (s.func == WIN_CUMCOUNT || s.func == WIN_ROLLING_COUNT) return false;
-  return c.nullable() || (is_rolling(s.func) && s.min_periods > 1);
+  if (s.func == WIN_CUMCOUNT || s.func == WIN_ROLLING_COUNT || s.func == WIN_RANGE_COUNT) return false;
+  return c.nullable() || (is_framed(s.func) && s.min_periods > 1);
 }
 
 // the new columns of an empty table
@@ -215,8 +263,8 @@ TablePtr Window(const TablePtr &t, const std::vector<int> &partition_cols, const
     if (s.func == WIN_ROW_NUMBER && !row_number.defined()) row_number = ex.empty_i64(n);
     if (s.func == WIN_RANK && !rank.defined()) rank = ex.empty_i64(n);
     if (s.func == WIN_DENSE_RANK && !dense_rank.defined()) dense_rank = ex.empty_i64(n);
-    if ((is_shift(s.func) || is_rolling(s.func)) && !phead.defined()) phead = ex.empty_i64(n);
-    if (is_rolling(s.func)) framed = true;
+    if ((is_shift(s.func) || is_framed(s.func)) && !phead.defined()) phead = ex.empty_i64(n);
+    if (is_framed(s.func)) framed = true;
   }
   if (row_number.defined() || rank.defined() || dense_rank.defined() || phead.defined()) {
     at::Tensor tagg = ex.empty_i64(3 * ntiles), tflag = ex.empty_u8(ntiles), carry = ex.empty_i64(3 * ntiles);
@@ -244,6 +292,84 @@ TablePtr Window(const TablePtr &t, const std::vector<int> &partition_cols, const
   int64_t frames_lds = 0, frames_wide = 0;
 
   std::map<int, Dense> dense;  // by value column
+  // the dense values of a column, gathered by its first user (window_tile's tile pairs are not used
+  // by the framed functions: COUNT suits every column)
+  auto dense_of = [&](int col) -> const Dense & {
+    auto it = dense.find(col);
+    if (it != dense.end()) return it->second;
+    const Column &c = t->column(col);
+    Dense d;
+    d.bits = ex.empty_i64(n);
+    if (c.nullable()) d.valid = ex.empty_u8(n);
+    at::Tensor tagg = ex.empty_i64(ntiles), tflag = ex.empty_u8(ntiles);
+    KCALL(ex, window_tile, c.view(), ptr<int64_t>(perm), ptr<uint8_t>(flags), n, kCount,
+          reinterpret_cast<uint64_t *>(ptr<int64_t>(d.bits)), d.valid.defined() ? ptr<uint8_t>(d.valid) : nullptr, true,
+          ptr<int64_t>(tagg), ptr<uint8_t>(tflag));
+    return dense.emplace(col, d).first->second;
+  };
+  auto u64 = [](const at::Tensor &x) { return reinterpret_cast<uint64_t *>(ptr<int64_t>(x)); };
+  auto u32 = [](const at::Tensor &x) { return reinterpret_cast<uint32_t *>(ptr<int64_t>(x)); };
+
+  // RANGE frames: the order column's search keys once, the bounds once per (preceding, following),
+  // a pyramid once per (column, operator)
+  struct Bounds {
+    at::Tensor lo, hi;  // n uint32 each
+  };
+  struct Pyramid {
+    at::Tensor P, S, E;
+  };
+  at::Tensor rkeys, rcls;
+  bool rfloat = false;
+  std::map<std::tuple<int, uint64_t, int, uint64_t>, Bounds> range_bounds;
+  std::map<std::pair<int, int>, Pyramid> pyramids;  // by (value column, kernel function)
+  int64_t range_specs = 0;
+  auto bounds_of = [&](const WindowSpec &s) -> const Bounds & {
+    if (!rkeys.defined()) {
+      const Column &oc = t->column(order_cols[0]);
+      rfloat = oc.type.kind() == ValueKind::FLOAT;
+      const Dense &d = dense_of(order_cols[0]);
+      rkeys = ex.empty_i64(n);
+      rcls = ex.empty_u8(n);
+      KCALL(ex, frame_range_keys, oc.view(), u64(d.bits), d.valid.defined() ? ptr<uint8_t>(d.valid) : nullptr, n,
+            !ck.asc[0], u64(rkeys), ptr<uint8_t>(rcls));
+    }
+    // a side: unbounded, an integer distance (integer keys) or a float64 one (float keys)
+    auto side = [&](int64_t i, double f, int *mode, uint64_t *ui, double *df) {
+      *ui = 0;
+      *df = 0;
+      if (i == kWindowUnbounded) {
+        *mode = FR_UNBOUNDED;
+      } else if (rfloat) {
+        *mode = FR_FLOAT;
+        *df = s.offset_is_float ? f : (double)i;
+      } else {
+        *mode = FR_INT;
+        *ui = (uint64_t)i;
+      }
+    };
+    int pm, fm;
+    uint64_t pi, fi;
+    double pf, ff;
+    side(s.preceding, s.preceding_f, &pm, &pi, &pf);
+    side(s.following, s.following_f, &fm, &fi, &ff);
+    const auto key = std::make_tuple(pm, rfloat ? fr_f64_bits(pf) : pi, fm, rfloat ? fr_f64_bits(ff) : fi);
+    auto it = range_bounds.find(key);
+    if (it != range_bounds.end()) return it->second;
+    Bounds b{ex.empty_i64((n + 1) / 2), ex.empty_i64((n + 1) / 2)};
+    KCALL(ex, frame_range_bounds, u64(rkeys), ptr<uint8_t>(rcls), ptr<int64_t>(phead), ptr<int64_t>(rtail), n, rfloat,
+          !ck.asc[0], pm, pi, pf, fm, fi, ff, u32(b.lo), u32(b.hi));
+    return range_bounds.emplace(key, b).first->second;
+  };
+  auto pyramid_of = [&](int col, int func) -> const Pyramid & {
+    auto it = pyramids.find({col, func});
+    if (it != pyramids.end()) return it->second;
+    const Dense &d = dense_of(col);
+    Pyramid p{ex.empty_i64(fr_ps_slots(n)), ex.empty_i64(fr_ps_slots(n)), ex.empty_i64(fr_e_slots(n))};
+    KCALL(ex, frame_range_pyramid, t->column(col).view(), n, func, u64(d.bits),
+          d.valid.defined() ? ptr<uint8_t>(d.valid) : nullptr, u64(p.P), u64(p.S), u64(p.E));
+    return pyramids.emplace(std::make_pair(col, func), p).first->second;
+  };
+
   std::vector<Column> out = t->columns();
   for (size_t i = 0; i < specs.size(); ++i) {
     const WindowSpec &s = specs[i];
@@ -263,6 +389,28 @@ TablePtr Window(const TablePtr &t, const std::vector<int> &partition_cols, const
     }
     const auto plan = value_plan(s, c);
     const bool nullable_out = nullable_result(s, c);
+    if (is_range(s.func)) {
+      const Bounds &b = bounds_of(s);
+      const Dense &d = dense_of(s.col);
+      const bool nulls = d.valid.defined();
+      // COUNT of a column without nulls is hi - lo + 1; with nulls the count pyramid also gives every
+      // other function its m
+      static const Pyramid none;
+      const Pyramid &cnt = nulls ? pyramid_of(s.col, kCount) : none;
+      const Pyramid &val = plan.first == kCount ? cnt : pyramid_of(s.col, plan.first);
+      Column col = make_fixed_column(name, plan.second, n, ex.device, nullable_out);
+      KCALL(ex, frame_range_apply, c.view(), ptr<int64_t>(perm), n, plan.first, s.func == WIN_RANGE_MEAN,
+            s.func == WIN_RANGE_COUNT ? 0 : s.min_periods, u64(d.bits), nulls ? ptr<uint8_t>(d.valid) : nullptr,
+            u32(b.lo), u32(b.hi), val.P.defined() ? u64(val.P) : nullptr, val.S.defined() ? u64(val.S) : nullptr,
+            val.E.defined() ? u64(val.E) : nullptr, cnt.P.defined() ? u64(cnt.P) : nullptr,
+            cnt.S.defined() ? u64(cnt.S) : nullptr, cnt.E.defined() ? u64(cnt.E) : nullptr,
+            reinterpret_cast<uint8_t *>(col.data.data_ptr()),
+            nullable_out ? col.validity.data_ptr<uint8_t>() : nullptr);
+      ++range_specs;
+      ++scans;
+      out.push_back(std::move(col));
+      continue;
+    }
     auto it = dense.find(s.col);
     const bool gather = it == dense.end();
     if (gather) {
@@ -332,6 +480,11 @@ TablePtr Window(const TablePtr &t, const std::vector<int> &partition_cols, const
   trace::add_counter("window.tiles", scans * ntiles);
   if (frames_lds) trace::add_counter("window.frame.lds", frames_lds);
   if (frames_wide) trace::add_counter("window.frame.wide", frames_wide);
+  if (range_specs) {
+    trace::add_counter("window.frame.range", range_specs);
+    trace::add_counter("window.range.bounds", (int64_t)range_bounds.size());
+    trace::add_counter("window.range.pyramids", (int64_t)pyramids.size());
+  }
   return Table::Make(t->GetContext(), std::move(out));
 }
 

@@ -87,7 +87,8 @@ struct SortOptions {
 
 // Window functions (docs/semantics.md "Window functions"), numbered as the C ABI and the bindings
 // pass them.  Functions 0 .. 8 have the frame ROWS BETWEEN UNBOUNDED PRECEDING AND CURRENT ROW; the
-// ROLLING functions have ROWS BETWEEN preceding PRECEDING AND following FOLLOWING.
+// ROLLING functions have ROWS BETWEEN preceding PRECEDING AND following FOLLOWING, the RANGE functions
+// RANGE BETWEEN preceding PRECEDING AND following FOLLOWING over the one order column.
 enum WindowFunc : int {
   WIN_ROW_NUMBER = 0,
   WIN_RANK = 1,
@@ -103,7 +104,14 @@ enum WindowFunc : int {
   WIN_ROLLING_MEAN = 11,
   WIN_ROLLING_MIN = 12,
   WIN_ROLLING_MAX = 13,
+  WIN_RANGE_COUNT = 14,
+  WIN_RANGE_SUM = 15,
+  WIN_RANGE_MEAN = 16,
+  WIN_RANGE_MIN = 17,
+  WIN_RANGE_MAX = 18,
 };
+
+constexpr int64_t kWindowUnbounded = INT64_MAX;  // a RANGE offset: no bound on that side
 
 struct WindowSpec {
   WindowFunc func;
@@ -115,6 +123,12 @@ struct WindowSpec {
   int64_t preceding = 0;
   int64_t following = 0;
   int64_t min_periods = 1;
+  // RANGE functions: preceding / following are distances in the order column's values (>= 0;
+  // kWindowUnbounded: no bound on that side).  offset_is_float: a side that is not unbounded reads
+  // its distance from preceding_f / following_f instead (float order columns only; >= 0, not NaN).
+  double preceding_f = 0;
+  double following_f = 0;
+  bool offset_is_float = false;
 };
 
 // As-of join (docs/semantics.md "As-of join"): every left row with the nearest right row of its group

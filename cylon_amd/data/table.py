@@ -375,12 +375,19 @@ class Table(PandasOpsMixin):
     # framed functions: they go through C.window_frames, which C.window's numbering stops short of
     _ROLLING_FUNCS = {"rolling_count": 9, "rolling_sum": 10, "rolling_mean": 11, "rolling_min": 12,
                       "rolling_max": 13}
+    # RANGE frames: they go through C.window_range_frames
+    _RANGE_FUNCS = {"range_count": 14, "range_sum": 15, "range_mean": 16, "range_min": 17, "range_max": 18}
     _UNBOUNDED = (1 << 63) - 1
 
     @classmethod
     def _is_rolling(cls, spec):
         return (not isinstance(spec, str) and len(spec) > 0 and isinstance(spec[0], str)
                 and spec[0].lower() in cls._ROLLING_FUNCS)
+
+    @classmethod
+    def _is_range(cls, spec):
+        return (not isinstance(spec, str) and len(spec) > 0 and isinstance(spec[0], str)
+                and spec[0].lower() in cls._RANGE_FUNCS)
 
     def _window_keys(self, partition_by, order_by, ascending):
         part = self._resolve_columns(partition_by) if partition_by is not None else []
@@ -415,6 +422,39 @@ class Table(PandasOpsMixin):
         pre, fol = (self._UNBOUNDED if b is None else int(b) for b in spec[2:4])
         return (self._ROLLING_FUNCS[fn], self._resolve_column(spec[1]), pre, fol,
                 int(spec[4]) if len(spec) == 5 else 1)
+
+    def _range_spec(self, spec):
+        """(WindowFunc number, value column, preceding, following, preceding_f, following_f, offset_is_float,
+        min_periods) of a range spec: a float offset makes the spec's offsets floats (an int beside it is
+        converted), None stays the integer that means unbounded"""
+        spec = tuple(spec)
+        fn = spec[0].lower()
+        if len(spec) < 4 or len(spec) > 5:
+            raise ValueError(f"window spec {spec!r}: expected ({fn!r}, column, preceding, following[, min_periods])")
+        for b in spec[2:4]:
+            if b is not None and (isinstance(b, bool) or not isinstance(b, (int, float))):
+                raise ValueError(f"window spec {spec!r}: an offset is an int, a float or None, not {b!r}")
+        is_float = any(isinstance(b, float) for b in spec[2:4])
+        ints = [self._UNBOUNDED if b is None else (0 if is_float else int(b)) for b in spec[2:4]]
+        floats = [float(b) if is_float and b is not None else 0.0 for b in spec[2:4]]
+        return (self._RANGE_FUNCS[fn], self._resolve_column(spec[1]), ints[0], ints[1], floats[0], floats[1], is_float,
+                int(spec[4]) if len(spec) == 5 else 1)
+
+    def _window_range_args(self, partition_by, order_by, ascending, funcs):
+        """_window_frame_args plus the float offsets, for a call with at least one range spec"""
+        part, order, asc = self._window_keys(partition_by, order_by, ascending)
+        lists = [[] for _ in range(10)]  # ids, cols, args, names, pre, fol, pre_f, fol_f, is_float, minp
+        for name, spec in (funcs or {}).items():
+            if self._is_range(spec):
+                fid, col, p, f, pf, ff, isf, m = self._range_spec(spec)
+                arg = 0
+            elif self._is_rolling(spec):
+                (fid, col, p, f, m), (arg, pf, ff, isf) = self._rolling_spec(spec), (0, 0.0, 0.0, False)
+            else:
+                (fid, col, arg), (p, f, pf, ff, isf, m) = self._window_spec(spec), (0, 0, 0.0, 0.0, False, 1)
+            for lst, v in zip(lists, (fid, col, arg, "" if name is None else str(name), p, f, pf, ff, isf, m)):
+                lst.append(v)
+        return (part, order, asc, *lists)
 
     def _window_args(self, partition_by, order_by, ascending, funcs):
         part, order, asc = self._window_keys(partition_by, order_by, ascending)
@@ -454,7 +494,20 @@ class Table(PandasOpsMixin):
         FOLLOWING of the partition: ("rolling_sum" | "rolling_mean" | "rolling_min" | "rolling_max" |
         "rolling_count", column, preceding, following[, min_periods = 1]), None meaning unbounded, e.g.
         ("rolling_mean", "v", 6, 0) for a 7-row moving average.  Nulls are skipped; the result is null
-        where the frame holds fewer than min_periods values (rolling_count is never null)."""
+        where the frame holds fewer than min_periods values (rolling_count is never null).
+
+        Range aggregates frame by the order column's VALUES instead, RANGE BETWEEN preceding PRECEDING AND
+        following FOLLOWING: ("range_sum" | "range_mean" | "range_min" | "range_max" | "range_count",
+        column, preceding, following[, min_periods = 1]) aggregates the rows of the partition whose order
+        value lies within `preceding` below and `following` above the row's own (the other way round
+        in a descending order), peers included.  They need exactly one order column -- an integer, a
+        temporal type (offsets in its unit) or float32 / float64; offsets are ints, floats (float
+        columns only) or None = unbounded, e.g. ("range_mean", "v", 5_000_000_000, 0) over a
+        timestamp[ns] column for the mean of the last 5 seconds (pandas rolling('5s', closed='both')
+        on unique timestamps).  Everything else is as for the rolling aggregates."""
+        if any(self._is_range(s) for s in (funcs or {}).values()):
+            return self._wrap(C.window_range_frames(self._t, *self._window_range_args(partition_by, order_by,
+                                                                                       ascending, funcs)))
         if any(self._is_rolling(s) for s in (funcs or {}).values()):
             return self._wrap(C.window_frames(self._t, *self._window_frame_args(partition_by, order_by, ascending,
                                                                                  funcs)))
@@ -463,7 +516,10 @@ class Table(PandasOpsMixin):
     def distributed_window(self, partition_by=None, order_by=None, ascending: Union[bool, List[bool]] = True,
                            funcs: dict = None) -> "Table":
         """window() after a shuffle by the partition columns (at least one when the world is larger than
-        1); the output row order is unspecified.  Rolling specs as in window()."""
+        1); the output row order is unspecified.  Rolling and range specs as in window()."""
+        if any(self._is_range(s) for s in (funcs or {}).values()):
+            return self._wrap(C.distributed_window_range_frames(
+                self._t, *self._window_range_args(partition_by, order_by, ascending, funcs)))
         if any(self._is_rolling(s) for s in (funcs or {}).values()):
             return self._wrap(C.distributed_window_frames(
                 self._t, *self._window_frame_args(partition_by, order_by, ascending, funcs)))

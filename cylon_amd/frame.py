@@ -407,7 +407,9 @@ class DataFrame(object):
         """Window functions (Table.window): ranking, running aggregates and lag / lead per partition, e.g.
         funcs={"rn": "row_number", "bal": ("cumsum", "amount"), "prev": ("lag", "amount", 1)}, and rolling
         aggregates over a ROWS frame, e.g. {"avg7": ("rolling_mean", "amount", 6, 0)} (the pandas
-        groupby().rolling(7, min_periods=1).mean()); a bound of None is unbounded.  With an env
+        groupby().rolling(7, min_periods=1).mean()), or over a RANGE frame of the order column's values, e.g.
+        {"sum5s": ("range_sum", "amount", 5_000_000_000, 0)} ordered by a timestamp[ns] column (the pandas
+        rolling('5s', closed='both') on unique timestamps); a bound of None is unbounded.  With an env
         of more than one rank the rows are first shuffled by the partition columns."""
         if env is None or env.world_size <= 1:
             return DataFrame(self._table.window(partition_by, order_by, ascending, funcs))

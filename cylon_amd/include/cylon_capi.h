@@ -68,6 +68,19 @@ int cylon_window_frames(const char *table_id, const int32_t *partition_columns, 
                         const int32_t *spec_columns, const int64_t *spec_args, const int64_t *preceding,
                         const int64_t *following, const int64_t *min_periods, const char *const *names, int nspecs,
                         int distributed, const char *dest_id);
+/* cylon_window_frames with RANGE frames too: also funcs[i] = 14 RANGE_COUNT, 15 RANGE_SUM, 16 RANGE_MEAN,
+   17 RANGE_MIN, 18 RANGE_MAX over RANGE BETWEEN preceding[i] PRECEDING AND following[i] FOLLOWING: the rows
+   of the partition whose value of the one order column (an integer, a temporal type, float32 or float64)
+   lies within those distances of the row's own, peers included.  preceding / following are in the
+   column's unit (>= 0), INT64_MAX: unbounded on that side.  offset_is_float[i] != 0 (float order
+   columns only): a side that is not unbounded reads preceding_f[i] / following_f[i] (>= 0, not NaN)
+   instead.  The three new arrays may be NULL (0, 0, false).  Functions 0..13 ignore them. */
+int cylon_window_range_frames(const char *table_id, const int32_t *partition_columns, int npartition,
+                              const int32_t *order_columns, const int32_t *ascending, int norder,
+                              const int32_t *funcs, const int32_t *spec_columns, const int64_t *spec_args,
+                              const int64_t *preceding, const int64_t *following, const double *preceding_f,
+                              const double *following_f, const int32_t *offset_is_float, const int64_t *min_periods,
+                              const char *const *names, int nspecs, int distributed, const char *dest_id);
 /* as-of join: every row of the left table, in its row order, with the columns of the nearest right row
    whose `by` columns equal its own (nby may be 0) -- direction 0 BACKWARD: the last right_on <=
    left_on, 1 FORWARD: the first right_on >= left_on, 2 NEAREST: the nearer of the two, the backward

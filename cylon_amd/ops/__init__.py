@@ -63,7 +63,8 @@ def window(t: Table, partition_by=None, order_by=None, ascending: Union[bool, Li
            funcs: dict = None) -> Table:
     """Table.window: ranking, running aggregates, lag / lead and rolling aggregates over a ROWS frame,
     ("rolling_sum" | "rolling_mean" | "rolling_min" | "rolling_max" | "rolling_count", column, preceding,
-    following[, min_periods])."""
+    following[, min_periods]), or over a RANGE frame of the one order column's values, ("range_sum" | ... |
+    "range_count", column, preceding, following[, min_periods])."""
     return t.window(partition_by, order_by, ascending, funcs)
 
 
