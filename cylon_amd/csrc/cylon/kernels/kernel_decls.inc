@@ -314,14 +314,16 @@ void radix_join_count(const int64_t *pkeys, const int64_t *poffs, const int64_t 
    rows from *cursor (int64, zeroed), claims past out_cap set *overflow |= 2, LDS overflow |= 1.
    pkey: index of the probe column that is the key itself (written from the probe key; -1 none).
    outer (see radix_join_count): bit 0 writes bpres[o] (1 = the build side holds a row), bit 1
-   writes ppres[o]; unmatched build rows follow their partition's matches */
-void radix_join_write(const int64_t *pkeys, const int64_t *poffs, const int64_t *bkeys, const int64_t *boffs,
+   writes ppres[o]; unmatched build rows follow their partition's matches.
+   Returns true when the exact-shape kernel ran (lds_join.hip k_rj_write_exact; never with exact_ok =
+   false), false for the generic one */
+bool radix_join_write(const int64_t *pkeys, const int64_t *poffs, const int64_t *bkeys, const int64_t *boffs,
                       int64_t nparts, int64_t cap, const int64_t *out_offs, const uint8_t *const *pin,
                       uint8_t *const *pout, const int *pw, int npc, const uint8_t *const *bin, uint8_t *const *bout,
                       const int *bw, int nbc, void *stream, int64_t *cursor = nullptr, int64_t out_cap = 0,
                       int *overflow = nullptr, int pkey = -1, int outer = 0, uint8_t *ppres = nullptr,
                       uint8_t *bpres = nullptr, int64_t pslot = 0, int64_t bslot = 0, const RJSplit *split = nullptr,
-                      const int64_t *narrow_base = nullptr);
+                      const int64_t *narrow_base = nullptr, bool exact_ok = true);
 /* K8 LDS radix group-by (GPU only; radix_groupby.hip) */
 int64_t distinct_estimate_workspace();  /* uint32 registers */
 double distinct_estimate(const int64_t *keys, int64_t n, uint32_t *regs, void *stream);

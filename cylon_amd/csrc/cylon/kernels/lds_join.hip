@@ -614,6 +614,242 @@ __global__ __launch_bounds__(kRJThreads, 4) void k_rj_write(const int64_t *__res
   }
 }
 
+// --------------------------------------------------------------------------
+// exact-shape write kernel
+// --------------------------------------------------------------------------
+// The inner join of all-8-byte columns whose probe column 0 is the key and whose build side
+// outputs only its staged payload columns (the key column is shared with the probe side), over
+// whole partitions (no split items): the column counts are template parameters, so the emit loop
+// is straight-line code on statically indexed kernel arguments.
+constexpr int kRJExactCols = 3;  // payload columns per side of the instantiated shapes: 1 .. 3
+struct ExactCols {
+  const uint64_t *pin[kRJExactCols];  // probe payload columns (partitioned order)
+  uint64_t *pout[kRJExactCols];
+  uint64_t *kout;                     // the key output column
+  const uint8_t *bin[kRJExactCols];   // build payload columns, staged in this order after keys + perm
+  uint64_t *bout[kRJExactCols];
+};
+
+// Probe once: phase C packs each probe row's result for phase D -- first matching slot i0 (13 bits:
+// < kRJMaxRows), pure (the matches are adjacent: match j is slot i0 + j), match count -- into one
+// register per round of the wave's slice, for the first kRJKeptRounds rounds; later rounds (a probe
+// partition beyond 16 * 64 * kRJKeptRounds rows) are probed again in phase D.
+constexpr int kRJKeptRounds = 8;
+constexpr uint32_t kRJPureBit = 1u << 13, kRJSlotMask = kRJPureBit - 1;
+constexpr int kRJCountShift = 14;
+static_assert(kRJMaxRows <= (int)kRJPureBit && kRJMaxRows < (1 << (32 - kRJCountShift)), "packed probe result");
+
+template <class KT>
+__device__ __forceinline__ uint32_t rj_probe_pack(const uint16_t *bst, const KT *skeys, KT k) {
+  const uint32_t b = rj_bucket(k);
+  uint32_t i0 = 0, last = 0, mc = 0;
+  for (uint32_t i = bst[b], e = bst[b + 1]; i < e; ++i)
+    if (skeys[i] == k) {
+      if (mc == 0) i0 = i;
+      last = i;
+      ++mc;
+    }
+  return i0 | (mc > 0 && last - i0 + 1 == mc ? kRJPureBit : 0u) | (mc << kRJCountShift);
+}
+
+// wave inclusive scan by DPP row shifts and row broadcasts (every lane active): no LDS round trip
+template <int CTRL, int ROWS>
+__device__ __forceinline__ uint32_t rj_dpp_add(uint32_t x) {
+  return x + (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, CTRL, ROWS, 0xF, false);
+}
+__device__ __forceinline__ uint32_t rj_wave_incscan(uint32_t x) {
+  x = rj_dpp_add<0x111, 0xF>(x);  // row_shr:1
+  x = rj_dpp_add<0x112, 0xF>(x);  // row_shr:2
+  x = rj_dpp_add<0x114, 0xF>(x);  // row_shr:4
+  x = rj_dpp_add<0x118, 0xF>(x);  // row_shr:8
+  x = rj_dpp_add<0x142, 0xA>(x);  // row_bcast:15 into rows 1 and 3
+  x = rj_dpp_add<0x143, 0xC>(x);  // row_bcast:31 into rows 2 and 3
+  return x;
+}
+
+template <int NP, int NB, bool NK>
+__global__ __launch_bounds__(kRJThreads, 4) void k_rj_write_exact(
+    const int64_t *__restrict__ pkeys0, const int64_t *__restrict__ poffs, const int64_t *__restrict__ bkeys0,
+    const int64_t *__restrict__ boffs, int64_t nparts, int cap, const int64_t *__restrict__ out_offs, ExactCols xc,
+    unsigned long long *__restrict__ cursor, int64_t out_cap, int *__restrict__ overflow, int64_t pslot,
+    int64_t bslot, const int64_t *__restrict__ narrow_base) {
+  // arguments, output placement (out_offs / cursor) and the LDS layout are k_rj_write's
+  static_assert(NP >= 1 && NP <= kRJExactCols && NB >= 1 && NB <= kRJExactCols, "exact shape");
+  using KT = typename std::conditional<NK, uint32_t, int64_t>::type;
+  const KT *__restrict__ pkeys = reinterpret_cast<const KT *>(pkeys0);
+  const KT *__restrict__ bkeys = reinterpret_cast<const KT *>(bkeys0);
+  const uint64_t nbase = NK ? (uint64_t)narrow_base[0] - (uint64_t(1) << 31) : 0;
+  __shared__ __attribute__((aligned(16))) uint16_t bst[kRJBuckets + 8];
+  __shared__ __attribute__((aligned(16))) uint8_t area[kRJRowArea];
+  __shared__ uint32_t wtot[kRJWaves];
+  __shared__ int64_t sclaim;
+  KT *skeys = reinterpret_cast<KT *>(area);
+  uint16_t *perm = reinterpret_cast<uint16_t *>(area + sizeof(KT) * (int64_t)cap);
+  const uint64_t *bcol = reinterpret_cast<const uint64_t *>(area + (int64_t)(sizeof(KT) + 2) * cap);  // column j at j * cap
+  const int lane = lane_id();
+  const int wave = threadIdx.x / kWave;
+  for (int64_t p = blockIdx.x; p < nparts; p += gridDim.x) {
+    int64_t rb, nr, lb, nl;
+    part_span(boffs, bslot, p, rb, nr);
+    part_span(poffs, pslot, p, lb, nl);
+    if (nr > cap && out_offs == nullptr && threadIdx.x == 0) atomicOr(overflow, 1);
+    if (nr == 0 || nl == 0 || nr > cap) continue;
+    // ---- phase A: the first probe round of this wave's slice into VGPRs (in flight during the build)
+    const int64_t per = (nl + kRJWaves - 1) / kRJWaves;
+    const int64_t s0 = lb + std::min<int64_t>(nl, wave * per);
+    const int64_t s1 = lb + std::min<int64_t>(nl, (wave + 1) * per);
+    KT pk0 = 0;
+    uint64_t pv0[NP] = {};
+    if (s0 + lane < s1) {
+      pk0 = pkeys[s0 + lane];
+#pragma unroll
+      for (int q = 0; q < NP; ++q) pv0[q] = xc.pin[q][s0 + lane];
+    }
+    // ---- phase B: stage + index the build rows (as k_rj_write with DMA staging)
+    __syncthreads();  // previous partition fully done with bst / area / wtot
+    for (int s = threadIdx.x; s < kRJBuckets / 2; s += blockDim.x) reinterpret_cast<uint32_t *>(bst)[s] = 0;
+    rj_dma(reinterpret_cast<const uint8_t *>(bkeys + rb), nr * (int)sizeof(KT), area, wave, lane);
+#pragma unroll
+    for (int j = 0; j < NB; ++j)
+      rj_dma(xc.bin[j] + rb * 8, nr * 8, area + (int64_t)(sizeof(KT) + 2) * cap + (int64_t)j * cap * 8, wave, lane);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    KT bk[kRJRowsPerThread];
+#pragma unroll
+    for (int i = 0; i < kRJRowsPerThread; ++i) {
+      const int r = threadIdx.x + i * kRJThreads;
+      if (r < nr) bk[i] = skeys[r];
+    }
+    uint32_t rk[kRJRowsPerThread];
+#pragma unroll
+    for (int i = 0; i < kRJRowsPerThread; ++i)
+      if (threadIdx.x + i * kRJThreads < nr) rk[i] = rj_claim(bst, rj_bucket(bk[i]));
+    __syncthreads();
+    rj_scan_buckets(bst, wtot);
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < kRJRowsPerThread; ++i) {
+      const int r = threadIdx.x + i * kRJThreads;
+      if (r < nr) {
+        const uint32_t pos = bst[rj_bucket(bk[i])] + rk[i];
+        skeys[pos] = bk[i];
+        perm[pos] = (uint16_t)r;
+      }
+    }
+    __syncthreads();
+    // ---- phase C: probe every row of the slice once; the first kRJKeptRounds rounds keep the result
+    uint32_t kept[kRJKeptRounds];
+#pragma unroll
+    for (int r = 0; r < kRJKeptRounds; ++r) kept[r] = 0;
+    if (s0 + lane < s1) kept[0] = rj_probe_pack<KT>(bst, skeys, pk0);
+#pragma unroll
+    for (int r = 1; r < kRJKeptRounds; r += 2) {  // two rounds' keys in flight before either probe
+      const int64_t l = s0 + r * kWave + lane;
+      if (s0 + r * kWave < s1) {  // uniform over the wave
+        const bool a = l < s1, b = r + 1 < kRJKeptRounds && l + kWave < s1;
+        KT ka = 0, kb = 0;
+        if (a) ka = pkeys[l];
+        if (b) kb = pkeys[l + kWave];
+        if (a) kept[r] = rj_probe_pack<KT>(bst, skeys, ka);
+        if (b) kept[r + 1 < kRJKeptRounds ? r + 1 : r] = rj_probe_pack<KT>(bst, skeys, kb);
+      }
+    }
+    uint32_t c = 0;
+#pragma unroll
+    for (int r = 0; r < kRJKeptRounds; ++r) c += kept[r] >> kRJCountShift;
+    {  // rounds past the kept ones: counted here, probed again in phase D
+      int64_t l = s0 + (int64_t)kRJKeptRounds * kWave + lane;
+      for (; l + kWave < s1; l += 2 * kWave) {
+        const KT ka = pkeys[l], kb = pkeys[l + kWave];
+        c += rj_count_mark<0, KT>(bst, skeys, ka, nullptr) + rj_count_mark<0, KT>(bst, skeys, kb, nullptr);
+      }
+      if (l < s1) c += rj_count_mark<0, KT>(bst, skeys, pkeys[l], nullptr);
+    }
+    for (int d = kWave / 2; d > 0; d >>= 1) c += __shfl_xor(c, d, kWave);
+    if (lane == 0) wtot[wave] = c;
+    __syncthreads();
+    int64_t base = out_offs ? out_offs[p] : 0;
+    if (out_offs == nullptr) {
+      if (threadIdx.x == 0) {
+        unsigned long long tot = 0;
+        for (int w = 0; w < kRJWaves; ++w) tot += wtot[w];
+        const unsigned long long at = tot ? atomicAdd(cursor, tot) : 0ull;
+        const bool fits = at + tot <= (unsigned long long)out_cap;
+        if (!fits) atomicOr(overflow, 2);
+        sclaim = fits ? (int64_t)at : -1;
+      }
+      __syncthreads();
+      base = sclaim;
+      if (base < 0) continue;  // uniform: the block's claim did not fit
+    }
+    for (int w = 0; w < wave; ++w) base += wtot[w];
+    // ---- phase D: emit.  Round u + 1's probe row is loaded while round u expands.
+    KT kn = pk0;
+    uint64_t vn[NP];
+#pragma unroll
+    for (int q = 0; q < NP; ++q) vn[q] = pv0[q];
+    for (int u = 0; s0 + (int64_t)u * kWave < s1; ++u) {
+      const int64_t l = s0 + (int64_t)u * kWave + lane;
+      const KT k = kn;
+      uint64_t v[NP];
+#pragma unroll
+      for (int q = 0; q < NP; ++q) v[q] = vn[q];
+      if (l + kWave < s1) {  // prefetch round u + 1
+        kn = pkeys[l + kWave];
+#pragma unroll
+        for (int q = 0; q < NP; ++q) vn[q] = xc.pin[q][l + kWave];
+      }
+      uint32_t word = 0;
+      if (u < kRJKeptRounds) {  // uniform
+#pragma unroll
+        for (int r = 0; r < kRJKeptRounds; ++r) word = u == r ? kept[r] : word;
+      } else if (l < s1) {
+        word = rj_probe_pack<KT>(bst, skeys, k);
+      }
+      const uint32_t inc = rj_wave_incscan(word >> kRJCountShift);  // inclusive output counts
+      const uint32_t wsum = __builtin_amdgcn_readlane(inc, kWave - 1);
+      // load-balanced expansion as in k_rj_write: lane t writes output rows base + t, base + 64 + t, ...
+      for (uint32_t t0 = 0; t0 < wsum; t0 += kWave) {
+        const uint32_t so = t0 + lane;
+        int owner = 0;
+#pragma unroll
+        for (int step = kWave / 2; step >= 1; step >>= 1) {
+          const uint32_t ic = __shfl(inc, owner + step - 1, kWave);
+          if (ic <= so) owner += step;
+        }
+        const uint32_t ow = __shfl(word, owner, kWave);
+        const uint32_t j = so + (ow >> kRJCountShift) - __shfl(inc, owner, kWave);  // match rank in the owner's bucket
+        const KT ko = rj_shfl_key(k, owner);
+        const uint64_t kw = NK ? nbase + (uint64_t)ko : (uint64_t)ko;
+        uint64_t vo[NP];
+#pragma unroll
+        for (int q = 0; q < NP; ++q) vo[q] = (uint64_t)rj_shfl64((int64_t)v[q], owner);
+        if (so < wsum) {
+          uint32_t slot = (ow & kRJSlotMask) + j;
+          if (!(ow & kRJPureBit)) {  // other keys between the matches: walk to match j
+            uint32_t i = ow & kRJSlotMask, m = 0;
+            const uint32_t e = bst[rj_bucket(ko) + 1];
+            for (; i < e; ++i)
+              if (skeys[i] == ko && m++ == j) break;
+            slot = i;
+          }
+          const uint32_t r = perm[slot];
+          uint64_t bv[NB];
+#pragma unroll
+          for (int q = 0; q < NB; ++q) bv[q] = bcol[(int64_t)q * cap + r];
+          const int64_t o = base + so;
+          xc.kout[o] = kw;
+#pragma unroll
+          for (int q = 0; q < NP; ++q) xc.pout[q][o] = vo[q];
+#pragma unroll
+          for (int q = 0; q < NB; ++q) xc.bout[q][o] = bv[q];
+        }
+      }
+      base += wsum;
+    }
+  }
+}
+
 static int rj_grid(int64_t nparts) { return (int)std::min<int64_t>(nparts, kNumCUs * 8); }
 
 void radix_join_count(const int64_t *pkeys, const int64_t *poffs, const int64_t *bkeys, const int64_t *boffs,
@@ -682,12 +918,26 @@ static void rj_write_launch(dim3 grid, hipStream_t s, const int64_t *pk, const i
                        sp.items, sp.nitems, sp.skip, sp.gprobe, sp.gbuild, nb);
 }
 
-void radix_join_write(const int64_t *pkeys, const int64_t *poffs, const int64_t *bkeys, const int64_t *boffs,
+// the exact-shape kernel for NP probe and NB build payload columns
+template <int NP, int NB>
+static void rj_write_exact_launch(dim3 grid, hipStream_t s, const int64_t *pk, const int64_t *poffs, const int64_t *bk,
+                                  const int64_t *boffs, int64_t nparts, int cap, const int64_t *out_offs,
+                                  const ExactCols &xc, unsigned long long *cur, int64_t out_cap, int *overflow,
+                                  int64_t pslot, int64_t bslot, const int64_t *nb) {
+  if (nb)
+    hipLaunchKernelGGL((k_rj_write_exact<NP, NB, true>), grid, dim3(kRJThreads), 0, s, pk, poffs, bk, boffs, nparts, cap,
+                       out_offs, xc, cur, out_cap, overflow, pslot, bslot, nb);
+  else
+    hipLaunchKernelGGL((k_rj_write_exact<NP, NB, false>), grid, dim3(kRJThreads), 0, s, pk, poffs, bk, boffs, nparts,
+                       cap, out_offs, xc, cur, out_cap, overflow, pslot, bslot, nb);
+}
+
+bool radix_join_write(const int64_t *pkeys, const int64_t *poffs, const int64_t *bkeys, const int64_t *boffs,
                       int64_t nparts, int64_t cap, const int64_t *out_offs, const uint8_t *const *pin,
                       uint8_t *const *pout, const int *pw, int npc, const uint8_t *const *bin, uint8_t *const *bout,
                       const int *bw, int nbc, void *stream, int64_t *cursor, int64_t out_cap, int *overflow, int pkey,
                       int outer, uint8_t *ppres, uint8_t *bpres, int64_t pslot, int64_t bslot,
-                      const RJSplit *split, const int64_t *narrow_base) {
+                      const RJSplit *split, const int64_t *narrow_base, bool exact_ok) {
   CYLON_CHECK(pkey >= -1 && pkey < npc, Code::Invalid, "radix join probe key column " << pkey);
   CYLON_CHECK(npc <= kMaxFusedCols && nbc <= kMaxFusedCols, Code::Invalid, "too many columns");
   CYLON_CHECK(out_offs != nullptr || (cursor != nullptr && overflow != nullptr), Code::Invalid,
@@ -698,7 +948,7 @@ void radix_join_write(const int64_t *pkeys, const int64_t *poffs, const int64_t 
   const RJSplit sp = split ? *split : RJSplit{};
   CYLON_CHECK(sp.nitems == 0 || (out_offs == nullptr && sp.items), Code::Invalid,
               "radix join write: split items need the cursor mode");
-  if (sp.nitems + nparts == 0) return;
+  if (sp.nitems + nparts == 0) return false;
   const int kbytes = narrow_base ? 4 : 8;
   CYLON_CHECK(cap > 0 && cap <= radix_join_capacity(bw, bin, nbc, outer & kOJBuild, kbytes), Code::Invalid,
               "radix join capacity " << cap);
@@ -739,6 +989,34 @@ void radix_join_write(const int64_t *pkeys, const int64_t *poffs, const int64_t 
   // LDS-DMA build staging: write kernel 33.9 -> 32.9 ms per 1B x 1B join (profiles/r03/lds_dma_ab.txt)
   const bool dma = w8;
   const int ci = (int)cap;
+  // Exact shapes: inner join, whole partitions only, every column 8 bytes, the probe key is column 0
+  // followed by 1 .. 3 payload columns, the build side outputs 1 .. 3 staged columns and no key.
+  if (exact_ok && outer == 0 && w8 && sp.nitems == 0 && sp.skip == nullptr && pkey == 0 && npc >= 2 &&
+      npc <= 1 + kRJExactCols && nbc >= 1 && nbc <= kRJExactCols && bs.n == nbc) {
+    ExactCols xc = {};
+    xc.kout = reinterpret_cast<uint64_t *>(pout[0]);
+    for (int q = 1; q < npc; ++q) {
+      xc.pin[q - 1] = reinterpret_cast<const uint64_t *>(pin[q]);
+      xc.pout[q - 1] = reinterpret_cast<uint64_t *>(pout[q]);
+    }
+    for (int q = 0; q < nbc; ++q) {
+      xc.bin[q] = bin[q];
+      xc.bout[q] = reinterpret_cast<uint64_t *>(bout[q]);
+    }
+#define RJX(NP_, NB_)                                                                                            \
+  case (NP_) * 4 + (NB_):                                                                                        \
+    rj_write_exact_launch<NP_, NB_>(grid, s, pkeys, poffs, bkeys, boffs, nparts, ci, out_offs, xc, cur, out_cap, \
+                                    overflow, pslot, bslot, narrow_base);                                        \
+    break
+    switch ((npc - 1) * 4 + nbc) {
+      RJX(1, 1); RJX(1, 2); RJX(1, 3);
+      RJX(2, 1); RJX(2, 2); RJX(2, 3);
+      RJX(3, 1); RJX(3, 2); RJX(3, 3);
+    }
+#undef RJX
+    HIP_LAUNCH_CHECK();
+    return true;
+  }
 #define RJW(W8_, DMA_, OJ_)                                                                                        \
   rj_write_launch<W8_, DMA_, OJ_>(grid, s, pkeys, poffs, bkeys, boffs, nparts, ci, out_offs, pc, bs, bo, cur, out_cap, \
                                   overflow, pkey, ppres, bpres, pslot, bslot, sp, narrow_base)
@@ -758,6 +1036,7 @@ void radix_join_write(const int64_t *pkeys, const int64_t *poffs, const int64_t 
   }
 #undef RJW
   HIP_LAUNCH_CHECK();
+  return false;
 }
 
 

@@ -298,6 +298,7 @@ struct Partitioned {
   RadixSide L, R;
   bool released = false;  // an input is gone: no fallback can run, the remaining failure exits raise
   SkewMasks sk;           // computed with the partition flags' read when no side was repartitioned
+  bool widened = false;   // a key left the narrowed range: repartitioned on 8-byte keys (generic write kernel)
 };
 
 // (a released input can no longer feed a fallback: the remaining failure exits raise instead)
@@ -391,6 +392,7 @@ static Partitioned partition_sides(const RadixJoinIn &in, RadixJoinPlan &plan, a
     trace::add_counter("join.radix.narrow_fallback", 1);
     plan = plan.without_narrowing();
     nkp = nullptr;
+    out.widened = true;
     L = radix_partition(ex, left, lk, bits, nullptr, slot_on ? plan.slot_l : 0);
     R = radix_partition(ex, right, rk, bits, nullptr, slot_on ? plan.slot_r : 0);
     if (L.slot || R.slot)
@@ -725,12 +727,15 @@ static void write_output(const RadixJoinIn &in, const JoinLaunch &jl, const Part
       if (pkey < 0) pkey = (int)q;
     }
   auto launch = [&](int64_t np, const int64_t *out_offs, const hip::RJSplit &sp) {
-    hip::radix_join_write(kptr(P.keys), ptr<int64_t>(P.offs), kptr(B.keys), ptr<int64_t>(B.offs), np, plan.cap(),
+    const bool exact =
+        hip::radix_join_write(kptr(P.keys), ptr<int64_t>(P.offs), kptr(B.keys), ptr<int64_t>(B.offs), np, plan.cap(),
                           out_offs, pc.in.data(), pc.out.data(), pc.w.data(), (int)pc.in.size(), bc.in.data(),
                           bc.out.data(), bc.w.data(), (int)bc.in.size(), jl.ex.stream, cursor, rows,
                           jl.overflow.data_ptr<int>(), pkey, plan.oj,
                           o.ppres.defined() ? o.ppres.data_ptr<uint8_t>() : nullptr,
-                          o.bpres.defined() ? o.bpres.data_ptr<uint8_t>() : nullptr, P.slot, B.slot, &sp, jl.nbase);
+                          o.bpres.defined() ? o.bpres.data_ptr<uint8_t>() : nullptr, P.slot, B.slot, &sp, jl.nbase,
+                          !pt.widened);
+    if (exact) trace::add_counter("join.radix.write_exact", 1);
   };
   launch(plan.nparts, offs, w.main);
   if (w.nemits > 0) launch(0, nullptr, w.emit);  // the deferred sides' unmatched rows, after every item recorded its matches
