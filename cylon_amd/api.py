@@ -62,6 +62,7 @@ def capi_library() -> ctypes.CDLL:
                                        i, i, s], i),
         "cylon_asof_join": ([s, s, i, i, pp(ctypes.c_int32), pp(ctypes.c_int32), i, i, i, i, i64, ctypes.c_double, s, s,
                              s, i], i),
+        "cylon_interval_join": ([s, s, i, i, i, pp(ctypes.c_int32), pp(ctypes.c_int32), i, i, i, s, s, s, i], i),
         "cylon_table_from_buffers": ([s, i, pp(s), pp(ctypes.c_int32), i64, pp(ctypes.c_void_p),
                                       pp(ctypes.c_void_p), pp(ctypes.c_void_p)], i),
         "cylon_select": ([s, ROW_PREDICATE, ctypes.c_void_p, s], i),

@@ -481,6 +481,67 @@ void register_extended_ops(py::module &m) {
       py::arg("left"), py::arg("right"), py::arg("left_on"), py::arg("right_on"), py::arg("left_by"),
       py::arg("right_by"), py::arg("direction") = 0, py::arg("allow_exact_matches") = true,
       py::arg("tolerance") = py::none(), py::arg("carry_step_tiles") = 0);
+  // interval join: closed 0 BOTH / 1 LEFT / 2 RIGHT / 3 NEITHER, how 0 INNER / 1 LEFT
+  auto interval_options = [](int closed, int how, const std::string &left_prefix, const std::string &right_prefix) {
+    IntervalOptions o;
+    o.closed = closed;
+    o.how = how;
+    o.left_prefix = left_prefix;
+    o.right_prefix = right_prefix;
+    return o;
+  };
+  m.def(
+      "interval_join",
+      [interval_options](const TablePtr &l, const TablePtr &r, int left_lower, int left_upper, int right_on,
+                         const std::vector<int> &left_by, const std::vector<int> &right_by, int closed, int how,
+                         const std::string &left_prefix, const std::string &right_prefix, int64_t carry_step_tiles) {
+        const IntervalOptions o = interval_options(closed, how, left_prefix, right_prefix);
+        py::gil_scoped_release nogil;
+        return ops::IntervalJoin(l, r, left_lower, left_upper, right_on, left_by, right_by, o, carry_step_tiles);
+      },
+      py::arg("left"), py::arg("right"), py::arg("left_lower"), py::arg("left_upper"), py::arg("right_on"),
+      py::arg("left_by"), py::arg("right_by"), py::arg("closed") = 0, py::arg("how") = 0,
+      py::arg("left_prefix") = "", py::arg("right_prefix") = "", py::arg("carry_step_tiles") = 0);
+  m.def(
+      "distributed_interval_join",
+      [interval_options](const TablePtr &l, const TablePtr &r, int left_lower, int left_upper, int right_on,
+                         const std::vector<int> &left_by, const std::vector<int> &right_by, int closed, int how,
+                         const std::string &left_prefix, const std::string &right_prefix) {
+        const IntervalOptions o = interval_options(closed, how, left_prefix, right_prefix);
+        py::gil_scoped_release nogil;
+        return ops::DistributedIntervalJoin(l, r, left_lower, left_upper, right_on, left_by, right_by, o);
+      },
+      py::arg("left"), py::arg("right"), py::arg("left_lower"), py::arg("left_upper"), py::arg("right_on"),
+      py::arg("left_by"), py::arg("right_by"), py::arg("closed") = 0, py::arg("how") = 0,
+      py::arg("left_prefix") = "", py::arg("right_prefix") = "");
+  // (li, ri): the pairs in the specified order, ri = -1 for the filler of a LEFT join:
+  // IntervalJoin is Gather(left, li) ++ GatherNullable(right, ri, how == LEFT)
+  m.def(
+      "interval_join_indices",
+      [interval_options](const TablePtr &l, const TablePtr &r, int left_lower, int left_upper, int right_on,
+                         const std::vector<int> &left_by, const std::vector<int> &right_by, int closed, int how,
+                         int64_t carry_step_tiles) {
+        const IntervalOptions o = interval_options(closed, how, "", "");
+        py::gil_scoped_release nogil;
+        return ops::IntervalJoinIndices(l, r, left_lower, left_upper, right_on, left_by, right_by, o, carry_step_tiles);
+      },
+      py::arg("left"), py::arg("right"), py::arg("left_lower"), py::arg("left_upper"), py::arg("right_on"),
+      py::arg("left_by"), py::arg("right_by"), py::arg("closed") = 0, py::arg("how") = 0,
+      py::arg("carry_step_tiles") = 0);
+  // the matches of every left row: the sort and the rank pass only
+  m.def(
+      "interval_join_counts",
+      [interval_options](const TablePtr &l, const TablePtr &r, int left_lower, int left_upper, int right_on,
+                         const std::vector<int> &left_by, const std::vector<int> &right_by, int closed,
+                         int64_t carry_step_tiles) {
+        const IntervalOptions o = interval_options(closed, 0, "", "");
+        py::gil_scoped_release nogil;
+        return ops::IntervalJoinCounts(l, r, left_lower, left_upper, right_on, left_by, right_by, o, carry_step_tiles);
+      },
+      py::arg("left"), py::arg("right"), py::arg("left_lower"), py::arg("left_upper"), py::arg("right_on"),
+      py::arg("left_by"), py::arg("right_by"), py::arg("closed") = 0, py::arg("carry_step_tiles") = 0);
+  // output rows per tile of the interval join's expansion (kernels/interval.hip); the CPU twin reports the same
+  m.def("interval_tile_rows", []() { return hip::interval_tile_rows(); });
   // rows per tile of the window scans and tiles per step of their carry scan (kernels/window.hip); the
   // CPU twin is one sequential loop and reports the same numbers
   m.def("window_tile_rows", []() { return hip::window_tile_rows(); });

@@ -256,6 +256,24 @@ CYLON_CAPI int cylon_asof_join(const char *left_id, const char *right_id, int le
   });
 }
 
+CYLON_CAPI int cylon_interval_join(const char *left_id, const char *right_id, int left_lower, int left_upper,
+                                   int right_on, const int32_t *left_by, const int32_t *right_by, int nby, int closed,
+                                   int how, const char *left_prefix, const char *right_prefix, const char *dest,
+                                   int distributed) {
+  return guard([&] {
+    if (nby < 0 || (nby > 0 && (left_by == nullptr || right_by == nullptr)))
+      return status(Status(Code::Invalid, "interval join: `by` columns"));
+    IntervalOptions o;
+    o.closed = closed;
+    o.how = how;
+    o.left_prefix = left_prefix ? left_prefix : "";
+    o.right_prefix = right_prefix ? right_prefix : "";
+    return status(IntervalJoinTables(left_id, right_id, left_lower, left_upper, right_on,
+                                     std::vector<int32_t>(left_by, left_by + nby),
+                                     std::vector<int32_t>(right_by, right_by + nby), o, dest, distributed != 0));
+  });
+}
+
 CYLON_CAPI int cylon_project(const char *id, const int32_t *cols, int n, const char *dest) {
   return guard([&] {
     TablePtr out;

@@ -120,6 +120,24 @@ Status DistributedAsofJoin(const TablePtr &left, const TablePtr &right, int left
                                    std::vector<int>(right_by.begin(), right_by.end()), options);
   });
 }
+Status IntervalJoin(const TablePtr &left, const TablePtr &right, int left_lower, int left_upper, int right_on,
+                    const std::vector<int32_t> &left_by, const std::vector<int32_t> &right_by,
+                    const IntervalOptions &options, TablePtr &out) {
+  return guard([&] {
+    out = ops::IntervalJoin(left, right, left_lower, left_upper, right_on,
+                            std::vector<int>(left_by.begin(), left_by.end()),
+                            std::vector<int>(right_by.begin(), right_by.end()), options);
+  });
+}
+Status DistributedIntervalJoin(const TablePtr &left, const TablePtr &right, int left_lower, int left_upper,
+                               int right_on, const std::vector<int32_t> &left_by,
+                               const std::vector<int32_t> &right_by, const IntervalOptions &options, TablePtr &out) {
+  return guard([&] {
+    out = ops::DistributedIntervalJoin(left, right, left_lower, left_upper, right_on,
+                                       std::vector<int>(left_by.begin(), left_by.end()),
+                                       std::vector<int>(right_by.begin(), right_by.end()), options);
+  });
+}
 Status Shuffle(const TablePtr &t, const std::vector<int> &cols, TablePtr &out) {
   return guard([&] { out = ops::Shuffle(t, cols); });
 }
@@ -328,6 +346,18 @@ Status AsofJoinTables(const std::string &left_id, const std::string &right_id, i
     const TablePtr l = GetTable(left_id), r = GetTable(right_id);
     PutTable(dest_id, distributed ? ops::DistributedAsofJoin(l, r, left_on, right_on, lby, rby, options)
                                   : ops::AsofJoin(l, r, left_on, right_on, lby, rby, options));
+  });
+}
+
+Status IntervalJoinTables(const std::string &left_id, const std::string &right_id, int left_lower, int left_upper,
+                          int right_on, const std::vector<int32_t> &left_by, const std::vector<int32_t> &right_by,
+                          const IntervalOptions &options, const std::string &dest_id, bool distributed) {
+  return guard([&] {
+    const std::vector<int> lby(left_by.begin(), left_by.end()), rby(right_by.begin(), right_by.end());
+    const TablePtr l = GetTable(left_id), r = GetTable(right_id);
+    PutTable(dest_id,
+             distributed ? ops::DistributedIntervalJoin(l, r, left_lower, left_upper, right_on, lby, rby, options)
+                         : ops::IntervalJoin(l, r, left_lower, left_upper, right_on, lby, rby, options));
   });
 }
 

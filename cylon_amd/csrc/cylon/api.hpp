@@ -74,6 +74,14 @@ Status AsofJoin(const TablePtr &left, const TablePtr &right, int left_on, int ri
 Status DistributedAsofJoin(const TablePtr &left, const TablePtr &right, int left_on, int right_on,
                            const std::vector<int32_t> &left_by, const std::vector<int32_t> &right_by,
                            const AsofOptions &options, TablePtr &out);
+// interval join (docs/semantics.md "Interval join"): every (left row, right row) pair of one group with
+// lower <= on <= upper
+Status IntervalJoin(const TablePtr &left, const TablePtr &right, int left_lower, int left_upper, int right_on,
+                    const std::vector<int32_t> &left_by, const std::vector<int32_t> &right_by,
+                    const IntervalOptions &options, TablePtr &out);
+Status DistributedIntervalJoin(const TablePtr &left, const TablePtr &right, int left_lower, int left_upper,
+                               int right_on, const std::vector<int32_t> &left_by,
+                               const std::vector<int32_t> &right_by, const IntervalOptions &options, TablePtr &out);
 Status Shuffle(const TablePtr &t, const std::vector<int> &hash_cols, TablePtr &out);
 Status HashPartition(const TablePtr &t, const std::vector<int> &hash_cols, int num_partitions,
                      std::map<int, TablePtr> *out);
@@ -170,6 +178,9 @@ Status WindowTable(const std::string &id, const std::vector<int32_t> &partition_
 Status AsofJoinTables(const std::string &left_id, const std::string &right_id, int left_on, int right_on,
                       const std::vector<int32_t> &left_by, const std::vector<int32_t> &right_by,
                       const AsofOptions &options, const std::string &dest_id, bool distributed);
+Status IntervalJoinTables(const std::string &left_id, const std::string &right_id, int left_lower, int left_upper,
+                          int right_on, const std::vector<int32_t> &left_by, const std::vector<int32_t> &right_by,
+                          const IntervalOptions &options, const std::string &dest_id, bool distributed);
 int64_t RowCount(const std::string &id);
 int32_t ColumnCount(const std::string &id);
 std::vector<std::string> ColumnNames(const std::string &id);

@@ -633,3 +633,31 @@ void asof_apply(const int64_t *perm, const uint8_t *restarts, const uint8_t *cod
 void asof_pick(const ColView &left_on, const ColView &right_on, int64_t nl, const int64_t *back, const int64_t *fwd,
                bool has_tolerance, int64_t tolerance_i, double tolerance_f, int64_t *match, int64_t *matched,
                void *stream);
+
+/* interval.hip (CPU twin cpu_interval.cpp): the interval join's rank pass, counts and expansion
+   (docs/semantics.md "Interval join").  perm = the stable sort of the n = nr + 2 nl concatenated key
+   rows (by .., value): the right rows (value = on) at [rbase, rbase + nr), the left rows' L-copies
+   (value = lower) at [lbase, lbase + nl) and their U-copies (value = upper) at [ubase, ubase + nl);
+   the three ranges tile [0, n).
+     interval_rank    with c(p) = the right rows strictly before sorted position p: an L-copy stores
+                      lo[left row] = c, a U-copy hi[left row] = c, a right row rrows[c] = its row
+                      number (the right side in sorted order).  On the device: a tile count over
+                      tiles of window_tile_rows() positions, window_carry (words 1, func 4, `step`
+                      tiles per loop step, <= 0: window_carry_tiles()) and the scattering re-scan; ws =
+                      interval_rank_workspace(n) int64 words.  perm must be 16-byte aligned.
+     interval_counts  cnt[l] = hi[l] - lo[l] where lower[l] and upper[l] are neither null nor NaN and
+                      hi > lo, else 0; *matched += their sum.  left: empty[l] = (cnt == 0) and cnt[l]
+                      becomes max(cnt, 1) (the filler row of a LEFT join); else empty may be nullptr.
+     interval_expand  off = the exclusive scan of cnt (nl + 1 entries, off[nl] = total).  Output row o
+                      of left row l (off[l] <= o < off[l + 1]) gets li[o] = l and
+                      ri[o] = rrows[lo[l] + (o - off[l])], or -1 where empty[l] (nullptr: no fillers).
+                      One block per tile of interval_tile_rows() output rows.
+   The CPU twin is the definition: three sequential loops; it ignores ws and step. */
+int64_t interval_tile_rows();
+int64_t interval_rank_workspace(int64_t n);
+void interval_rank(const int64_t *perm, int64_t nl, int64_t nr, int64_t lbase, int64_t rbase, int64_t ubase,
+                   int64_t step, int64_t *ws, int64_t *lo, int64_t *hi, int64_t *rrows, void *stream);
+void interval_counts(const ColView &lower, const ColView &upper, const int64_t *lo, const int64_t *hi, int64_t nl,
+                     bool left, int64_t *cnt, uint8_t *empty, int64_t *matched, void *stream);
+void interval_expand(const int64_t *off, const int64_t *lo, const uint8_t *empty, const int64_t *rrows, int64_t nl,
+                     int64_t nr, int64_t total, int64_t *li, int64_t *ri, void *stream);

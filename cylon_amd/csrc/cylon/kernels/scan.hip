@@ -328,6 +328,7 @@ void preload_frame_range();
 void preload_groupby();
 void preload_hash_join();
 void preload_index();
+void preload_interval();
 void preload_lds_join();
 void preload_merge();
 void preload_partition();
@@ -357,6 +358,7 @@ void preload_device_code() {
   preload_groupby();
   preload_hash_join();
   preload_index();
+  preload_interval();
   preload_lds_join();
   preload_merge();
   preload_partition();

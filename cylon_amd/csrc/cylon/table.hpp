@@ -147,6 +147,17 @@ struct AsofOptions {
   std::string left_prefix, right_prefix;
 };
 
+// Interval join (docs/semantics.md "Interval join"): every pair of a left row and a right row of its
+// group whose `on` value lies between the left row's `lower` and `upper`.
+enum IntervalClosed : int { INTERVAL_BOTH = 0, INTERVAL_LEFT = 1, INTERVAL_RIGHT = 2, INTERVAL_NEITHER = 3 };
+enum IntervalHow : int { INTERVAL_INNER = 0, INTERVAL_LEFT_OUTER = 1 };
+
+struct IntervalOptions {
+  int closed = INTERVAL_BOTH;  // an IntervalClosed: which ends of [lower, upper] belong to the interval
+  int how = INTERVAL_INNER;    // an IntervalHow; any other number of either is Invalid
+  std::string left_prefix, right_prefix;
+};
+
 namespace ops {
 
 // ---- plumbing -------------------------------------------------------------
@@ -271,6 +282,28 @@ TablePtr AsofJoin(const TablePtr &left, const TablePtr &right, int left_on, int 
 TablePtr DistributedAsofJoin(const TablePtr &left, const TablePtr &right, int left_on, int right_on,
                              const std::vector<int> &left_by, const std::vector<int> &right_by,
                              const AsofOptions &options);
+// Interval join (ops/interval.cpp): all of left's columns, then all of right's (names get the prefixes
+// as Join's do), one row per pair of a left row and a right row of the same `by` group with lower <=
+// on <= upper (`closed` opens either end); rows ordered by left row, then right `on`, then right row.
+// how = LEFT adds one row with null right columns, in its place, for a left row without a match.
+// Neither input needs to be sorted.  IntervalJoinIndices: the (left row, right row) pairs in that
+// order, right row -1 for a LEFT filler.  IntervalJoinCounts: the matches of every left row (sort and
+// rank pass only; `how` does not change them).  carry_step_tiles > 0 (tests only) lowers the tiles one
+// step of the rank pass's carry scan covers.  DistributedIntervalJoin: shuffle both sides by their
+// `by` columns (at least one), then IntervalJoin on every rank; the output row order is unspecified.
+std::pair<at::Tensor, at::Tensor> IntervalJoinIndices(const TablePtr &left, const TablePtr &right, int left_lower,
+                                                      int left_upper, int right_on, const std::vector<int> &left_by,
+                                                      const std::vector<int> &right_by,
+                                                      const IntervalOptions &options, int64_t carry_step_tiles = 0);
+at::Tensor IntervalJoinCounts(const TablePtr &left, const TablePtr &right, int left_lower, int left_upper,
+                              int right_on, const std::vector<int> &left_by, const std::vector<int> &right_by,
+                              const IntervalOptions &options, int64_t carry_step_tiles = 0);
+TablePtr IntervalJoin(const TablePtr &left, const TablePtr &right, int left_lower, int left_upper, int right_on,
+                      const std::vector<int> &left_by, const std::vector<int> &right_by,
+                      const IntervalOptions &options, int64_t carry_step_tiles = 0);
+TablePtr DistributedIntervalJoin(const TablePtr &left, const TablePtr &right, int left_lower, int left_upper,
+                                 int right_on, const std::vector<int> &left_by, const std::vector<int> &right_by,
+                                 const IntervalOptions &options);
 
 }  // namespace ops
 }  // namespace cylon

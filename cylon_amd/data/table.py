@@ -585,6 +585,61 @@ class Table(PandasOpsMixin):
                                tolerance)
         return self._wrap(C.distributed_asof_join(self._t, table._t, *args, left_prefix, right_prefix))
 
+    _INTERVAL_CLOSED = {"both": 0, "left": 1, "right": 2, "neither": 3}
+    _INTERVAL_HOW = {"inner": 0, "left": 1}
+
+    def _interval_args(self, table: "Table", lower, upper, on, by, left_by, right_by, closed, how=None):
+        """-> (lower, upper, on, left_by, right_by, closed[, how]) as the engine takes them"""
+        if any(c is None or isinstance(c, (list, tuple)) for c in (lower, upper, on)):
+            raise ValueError("interval_join needs one `lower`, one `upper` and one `on` column")
+        if by is not None:
+            left_by = right_by = by
+        as_list = lambda b: [] if b is None else (list(b) if isinstance(b, (list, tuple)) else [b])
+        lby, rby = as_list(left_by), as_list(right_by)
+        if len(lby) != len(rby):
+            raise ValueError(f"interval_join: {len(lby)} left and {len(rby)} right `by` columns")
+        if isinstance(closed, str):
+            if closed.lower() not in self._INTERVAL_CLOSED:
+                raise ValueError(f"unknown closed {closed!r}; one of {sorted(self._INTERVAL_CLOSED)}")
+            closed = self._INTERVAL_CLOSED[closed.lower()]
+        args = (self._asof_column(lower), self._asof_column(upper), table._asof_column(on),
+                [self._asof_column(c) for c in lby], [table._asof_column(c) for c in rby], int(closed))
+        if how is None:
+            return args
+        if isinstance(how, str):
+            if how.lower() not in self._INTERVAL_HOW:
+                raise ValueError(f"unknown interval join type {how!r}; one of {sorted(self._INTERVAL_HOW)}")
+            how = self._INTERVAL_HOW[how.lower()]
+        return args + (int(how),)
+
+    def interval_join(self, table: "Table", lower, upper, on, by=None, left_by=None, right_by=None,
+                      closed: str = "both", how: str = "inner", left_prefix: str = "",
+                      right_prefix: str = "") -> "Table":
+        """Interval join (SQL `r.on BETWEEN l.lower AND l.upper`, a range join): one row for every pair of a
+        row of this table and a row of `table` whose `by` columns equal its own and whose `on` value lies
+        in [lower, upper] -- this table's columns, then `table`'s.  closed: "both", "left" (lower <= on <
+        upper), "right" or "neither".  Rows are ordered by this table's row, then `on`, then `table`'s
+        row.  how="left" adds one row with null right columns for a row without a match.  A null or NaN
+        bound or `on` never matches; +-inf and the integer extremes are ordinary values, which is how an
+        unbounded side is written (docs/semantics.md "Interval join")."""
+        args = self._interval_args(table, lower, upper, on, by, left_by, right_by, closed, how)
+        return self._wrap(C.interval_join(self._t, table._t, *args, left_prefix, right_prefix))
+
+    def distributed_interval_join(self, table: "Table", lower, upper, on, by=None, left_by=None, right_by=None,
+                                  closed: str = "both", how: str = "inner", left_prefix: str = "",
+                                  right_prefix: str = "") -> "Table":
+        """interval_join() after a shuffle of both tables by their `by` columns (at least one when the world
+        is larger than 1); the output row order is unspecified."""
+        args = self._interval_args(table, lower, upper, on, by, left_by, right_by, closed, how)
+        return self._wrap(C.distributed_interval_join(self._t, table._t, *args, left_prefix, right_prefix))
+
+    def interval_join_counts(self, table: "Table", lower, upper, on, by=None, left_by=None, right_by=None,
+                             closed: str = "both") -> torch.Tensor:
+        """How many rows of `table` fall into each row's interval: an int64 tensor of one count per row of
+        this table, on its device.  The pairs themselves are never built."""
+        args = self._interval_args(table, lower, upper, on, by, left_by, right_by, closed)
+        return C.interval_join_counts(self._t, table._t, *args)
+
     def shuffle(self, hash_columns: List = None) -> "Table":
         return self._wrap(C.shuffle(self._t, self._resolve_columns(hash_columns)))
 

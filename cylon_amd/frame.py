@@ -431,6 +431,21 @@ class DataFrame(object):
         right._change_context(env)
         return DataFrame(self._table.distributed_asof_join(right._table, **kw))
 
+    def merge_interval(self, right: "DataFrame", lower, upper, on, by=None, left_by=None, right_by=None,
+                       closed: str = "both", how: str = "inner", suffixes=("_x", "_y"),
+                       env: CylonEnv = None) -> "DataFrame":
+        """Interval join through Table.interval_join: every pair of a row of this frame and a row of `right`
+        of the same `by` group whose `on` value lies in the row's [lower, upper].  As in merge(), the
+        suffixes are applied as prefixes to every column of their side.  With an env of more than one rank
+        both frames are first shuffled by their `by` columns."""
+        kw = dict(lower=lower, upper=upper, on=on, by=by, left_by=left_by, right_by=right_by, closed=closed, how=how,
+                  left_prefix=suffixes[0], right_prefix=suffixes[1])
+        if env is None or env.world_size <= 1:
+            return DataFrame(self._table.interval_join(right._table, **kw))
+        self._change_context(env)
+        right._change_context(env)
+        return DataFrame(self._table.distributed_interval_join(right._table, **kw))
+
     def groupby(self, by, agg: dict, algorithm: str = "hash", env: CylonEnv = None) -> "DataFrame":
         if env is None:
             return DataFrame(self._table.local_groupby(by, agg, algorithm))

@@ -92,6 +92,15 @@ int cylon_asof_join(const char *left_id, const char *right_id, int left_on, int 
                     const int32_t *right_by, int nby, int direction, int allow_exact, int has_tolerance,
                     int64_t tolerance_i, double tolerance_f, const char *left_prefix, const char *right_prefix,
                     const char *dest_id, int distributed);
+/* interval join: one row per pair of a left row and a right row whose `by` columns equal its own (nby
+   may be 0) and whose `on` value lies in the left row's [lower, upper] -- closed 0 BOTH, 1 LEFT (lower
+   <= on < upper), 2 RIGHT (lower < on <= upper), 3 NEITHER; rows ordered by left row, then right `on`,
+   then right row.  how 0 INNER, 1 LEFT: a left row without a match gives one row with null right
+   columns.  A null or NaN bound or `on` never matches; names get the prefixes (NULL: none).
+   distributed != 0 needs a `by` column at world sizes > 1. */
+int cylon_interval_join(const char *left_id, const char *right_id, int left_lower, int left_upper, int right_on,
+                        const int32_t *left_by, const int32_t *right_by, int nby, int closed, int how,
+                        const char *left_prefix, const char *right_prefix, const char *dest_id, int distributed);
 int cylon_project(const char *table_id, const int32_t *columns, int ncolumns, const char *dest_id);
 
 int cylon_merge(const char *const *table_ids, int ntables, const char *dest_id);

@@ -83,6 +83,16 @@ def distributed_asof_join(left: Table, right: Table, **kwargs) -> Table:
     return left.distributed_asof_join(right, **kwargs)
 
 
+def interval_join(left: Table, right: Table, lower, upper, on, **kwargs) -> Table:
+    """Table.interval_join: lower, upper (columns of left), on (a column of right); by= | left_by=, right_by=;
+    closed, how, left_prefix, right_prefix."""
+    return left.interval_join(right, lower, upper, on, **kwargs)
+
+
+def distributed_interval_join(left: Table, right: Table, lower, upper, on, **kwargs) -> Table:
+    return left.distributed_interval_join(right, lower, upper, on, **kwargs)
+
+
 def shuffle(t: Table, hash_columns: List = None) -> Table:
     return t.shuffle(hash_columns)
 
@@ -118,5 +128,6 @@ def merge(tables: Sequence[Table]) -> Table:
 
 __all__ = ["join", "distributed_join", "union", "subtract", "intersect", "distributed_union",
            "distributed_subtract", "distributed_intersect", "sort", "distributed_sort", "topk",
-           "distributed_topk", "window", "distributed_window", "asof_join", "distributed_asof_join", "shuffle",
+           "distributed_topk", "window", "distributed_window", "asof_join", "distributed_asof_join", "interval_join",
+           "distributed_interval_join", "shuffle",
            "hash_partition", "unique", "distributed_unique", "groupby", "local_groupby", "project", "merge"]
