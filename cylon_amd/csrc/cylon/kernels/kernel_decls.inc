@@ -607,6 +607,60 @@ void frame_range_apply(const ColView &col, const int64_t *perm, int64_t n, int f
                        const uint64_t *P, const uint64_t *S, const uint64_t *E, const uint64_t *cP,
                        const uint64_t *cS, const uint64_t *cE, uint8_t *out, uint8_t *out_valid, void *stream);
 
+/* window_nav.hip (CPU twin cpu_window_nav.cpp): FIRST / LAST / NTH_VALUE, FFILL / BFILL, NTILE,
+   PERCENT_RANK and CUME_DIST (docs/semantics.md "Navigation and distribution functions") from what the
+   window operator already has: perm, the flags, the dense values and validity bytes of window_tile,
+   phead, and rtail (the tail of position i is n - 1 - rtail[n - 1 - i]).
+   The fill scan is the segmented running maximum of "scan position + 1 where the dense validity byte
+   is set, else 0".  reverse = false: scan position k is sorted position k and restarts = the flags
+   (bit 0); reverse = true: it is sorted position n - 1 - k and restarts = window_rev_flags' (or
+   window_rev_peer_flags') output.  Three launches over tiles of window_tile_rows() positions:
+     window_fill_tile   one (flag, aggregate) pair per tile.  dense_valid must not be nullptr: a column
+                        without nulls needs no scan.
+     window_carry       (words 1, func 3): each tile's carry-in.
+     window_fill_apply  re-scans each tile.  The source of sorted position i is the nearest non-null
+                        position j at or before it (reverse: at or after it) in its partition; there is
+                        none when no such j exists or, for limit > 0, when it is more than limit
+                        positions away.  Every output that is not nullptr is written (out and src
+                        exclude each other):
+                          out / out_valid (value mode, col's width 1, 2, 4 or 8): out[perm[i]] = dense[j],
+                            out_valid[perm[i]] = 1; without a source out_valid[perm[i]] = 0 and the
+                            value bytes are dense[i];
+                          src (source mode): src[perm[i]] = perm[j], or -1;
+                          pos: pos[i] = j, or -1, in sorted order.
+   window_nav_pick: one sorted position j per row, form 0 FIRST_VALUE: phead[i]; 1 LAST_VALUE: tail[i];
+   2 NTH_VALUE: phead[i] + k - 1 when <= tail[i], else none; 3 FIRST_VALUE ignoring nulls:
+   fillpos[phead[i]] with fillpos = the pos of a reversed fill; 4 LAST_VALUE ignoring nulls:
+   fillpos[tail[i]] with the pos of a forward one.  Value mode (out, out_valid): out[perm[i]] = dense[j],
+   out_valid[perm[i]] = dense_valid[j] (1 when nullptr), 0 without a j; source mode (src):
+   src[perm[i]] = perm[j] or -1.  phead may be nullptr for form 1, rtail for forms 0 and 3.
+   window_rev_peer_flags: as window_rev_flags, and bit 1 is set where sorted position n - 1 - k ends a
+   run of peers (bit 0 where it ends a partition; a partition's end ends a run of peers too).
+   window_rank_heads: the apply of the rank scan (window_rank_tile / window_carry(words 3, func 5) over
+   `flags`) that stores, in scan order, phead[k] = the last position with bit 0 at or before k and
+   qhead[k] = the last one with bit 1 (either may be nullptr).  Over the flags qhead is the head of
+   position k's peers (RANK = qhead - phead + 1); over window_rev_peer_flags' output the last peer of
+   sorted position i is n - 1 - qhead[n - 1 - i].
+   window_dist_apply: func 0 NTILE(k) (int64), 1 PERCENT_RANK, 2 CUME_DIST (float64), out[perm[i]].  With
+   s = tail - phead + 1 and r = i - phead: NTILE as docs/semantics.md spells it out; PERCENT_RANK =
+   (qhead[i] - phead[i]) / (s - 1), 0 when s == 1; CUME_DIST = (last peer - phead[i] + 1) / s; each one
+   float64 division of two exactly converted integers.  qhead: func 1, rqhead: func 2, else nullptr.
+   The CPU twin is the definition: its window_fill_tile does nothing, every other function is one
+   sequential loop. */
+void window_fill_tile(const uint8_t *restarts, int64_t n, bool reverse, const uint8_t *dense_valid,
+                      int64_t *tile_agg, uint8_t *tile_flag, void *stream);
+void window_fill_apply(const ColView &col, const int64_t *perm, const uint8_t *restarts, int64_t n, bool reverse,
+                       int64_t limit, const uint64_t *dense, const uint8_t *dense_valid, const int64_t *carry,
+                       uint8_t *out, uint8_t *out_valid, int64_t *src, int64_t *pos, void *stream);
+void window_nav_pick(const ColView &col, const int64_t *perm, const int64_t *phead, const int64_t *rtail,
+                     const int64_t *fillpos, int64_t n, int form, int64_t k, const uint64_t *dense,
+                     const uint8_t *dense_valid, uint8_t *out, uint8_t *out_valid, int64_t *src, void *stream);
+void window_rev_peer_flags(const uint8_t *flags, int64_t n, uint8_t *rflags, void *stream);
+void window_rank_heads(const uint8_t *flags, int64_t n, const int64_t *carry, int64_t *phead, int64_t *qhead,
+                       void *stream);
+void window_dist_apply(const int64_t *perm, const int64_t *phead, const int64_t *rtail, const int64_t *qhead,
+                       const int64_t *rqhead, int64_t n, int func, int64_t k, uint8_t *out, void *stream);
+
 /* asof.hip (CPU twin cpu_asof.cpp): the as-of join's scan over the merged order of both sides' key
    rows (docs/semantics.md "As-of join").  perm = the stable sort of the n concatenated key rows, the
    first nfirst of them from one side; sorted position i holds a right row where

@@ -345,6 +345,7 @@ void preload_sort();
 void preload_strcast();
 void preload_topk();
 void preload_window();
+void preload_window_nav();
 
 // Every kernel file's code object, once per process and device (HIP loads a code object on the first
 // launch from it: inside a pipelined join that stalled the host for up to 40 ms while the posted
@@ -376,6 +377,7 @@ void preload_device_code() {
   preload_strcast();
   preload_topk();
   preload_window();
+  preload_window_nav();
 }
 
 }  // namespace hip

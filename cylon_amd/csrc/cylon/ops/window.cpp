@@ -18,6 +18,14 @@
 // is gathered like a value column and turned into search keys once per call; every distinct
 // (preceding, following) gets one bounds search (lo / hi per sorted position), every (column, operator)
 // one scan pyramid, and a spec is then one query launch of kernels/frame_range.hip.
+//
+// The navigation and distribution functions (kernels/window_nav.hip) share all of that as well.  FFILL /
+// BFILL and the IGNORE NULLS forms of FIRST / LAST_VALUE scan "the last non-null position" over the
+// dense validity bytes, once per (column, direction) whatever the number of specs; a column without a
+// validity array is answered without a scan.  FIRST / LAST / NTH_VALUE are one element-wise launch over
+// phead / rtail, the distribution functions one over phead, rtail and the peer heads / tails that the
+// two rank scans carry anyway.  Columns of width 1, 2, 4 or 8 are written straight from the dense
+// values (value mode); every other type goes through a source-row array and GatherColumn.
 #include <algorithm>
 #include <map>
 #include <set>
@@ -57,6 +65,14 @@ const char *func_name(WindowFunc f) {
     case WIN_RANGE_MEAN: return "range_mean";
     case WIN_RANGE_MIN: return "range_min";
     case WIN_RANGE_MAX: return "range_max";
+    case WIN_FIRST_VALUE: return "first_value";
+    case WIN_LAST_VALUE: return "last_value";
+    case WIN_NTH_VALUE: return "nth_value";
+    case WIN_FFILL: return "ffill";
+    case WIN_BFILL: return "bfill";
+    case WIN_NTILE: return "ntile";
+    case WIN_PERCENT_RANK: return "percent_rank";
+    case WIN_CUME_DIST: return "cume_dist";
   }
   CYLON_THROW(Code::Invalid, "window function " << static_cast<int>(f));
 }
@@ -66,6 +82,13 @@ bool is_shift(WindowFunc f) { return f == WIN_LAG || f == WIN_LEAD; }
 bool is_rolling(WindowFunc f) { return f >= WIN_ROLLING_COUNT && f <= WIN_ROLLING_MAX; }
 bool is_range(WindowFunc f) { return f >= WIN_RANGE_COUNT && f <= WIN_RANGE_MAX; }
 bool is_framed(WindowFunc f) { return is_rolling(f) || is_range(f); }
+bool is_pick(WindowFunc f) { return f >= WIN_FIRST_VALUE && f <= WIN_NTH_VALUE; }
+bool is_fill(WindowFunc f) { return f == WIN_FFILL || f == WIN_BFILL; }
+bool is_dist(WindowFunc f) { return f >= WIN_NTILE && f <= WIN_CUME_DIST; }
+bool no_column(WindowFunc f) { return is_ranking(f) || is_dist(f); }
+// what a navigation or distribution function reads of the two rank scans
+bool nav_needs_phead(WindowFunc f) { return f == WIN_FIRST_VALUE || f == WIN_NTH_VALUE || is_dist(f); }
+bool nav_needs_rtail(WindowFunc f) { return f == WIN_LAST_VALUE || f == WIN_NTH_VALUE || is_dist(f); }
 // the ROLLING function whose result rules a RANGE function shares
 WindowFunc rolling_twin(WindowFunc f) {
   return is_range(f) ? static_cast<WindowFunc>(f - WIN_RANGE_COUNT + WIN_ROLLING_COUNT) : f;
@@ -79,6 +102,13 @@ bool range_order_type(const Column &c) {
     case Type::TIMESTAMP: case Type::TIME32: case Type::TIME64: case Type::DURATION: return !c.is_var();
     default: return false;
   }
+}
+
+// a column whose cells the navigation kernels copy themselves (value mode)
+bool nav_value_mode(const Column &c) {
+  if (c.is_var()) return false;
+  const int w = c.type.width();
+  return w == 1 || w == 2 || w == 4 || w == 8;
 }
 
 bool scan_value(const Column &c) {
@@ -128,8 +158,9 @@ Checked check(const TablePtr &t, const std::vector<int> &part, const std::vector
   for (const auto &s : specs) {
     const char *fn = func_name(s.func);
     std::string name = s.name;
-    if (is_ranking(s.func)) {
+    if (no_column(s.func)) {
       if (name.empty()) name = fn;
+      if (s.func == WIN_NTILE) CYLON_CHECK(s.arg >= 1, Code::Invalid, "window ntile of " << s.arg << " buckets");
     } else {
       CYLON_CHECK(s.col >= 0 && s.col < t->Columns(), Code::Invalid, "window " << fn << " of column " << s.col);
       const Column &c = t->column(s.col);
@@ -138,6 +169,11 @@ Checked check(const TablePtr &t, const std::vector<int> &part, const std::vector
         CYLON_CHECK(scan_value(c) && !(s.func == WIN_CUMSUM && c.type.type == Type::HALF_FLOAT), Code::Invalid,
                     "window " << fn << " needs a fixed-width numeric column, got " << c.type.ToString());
       if (is_shift(s.func)) CYLON_CHECK(s.arg >= 0, Code::Invalid, "window " << fn << " offset " << s.arg << " < 0");
+      if (s.func == WIN_NTH_VALUE) {
+        CYLON_CHECK(s.arg >= 1, Code::Invalid, "window nth_value of row " << s.arg << " < 1");
+        CYLON_CHECK(!s.ignore_nulls, Code::Invalid, "window nth_value does not take ignore_nulls");
+      }
+      if (is_fill(s.func)) CYLON_CHECK(s.limit >= 0, Code::Invalid, "window " << fn << " limit " << s.limit << " < 0");
       if (is_framed(s.func)) {
         const WindowFunc rf = rolling_twin(s.func);
         CYLON_CHECK(t->Rows() < (int64_t(1) << 32), Code::Invalid,
@@ -180,8 +216,12 @@ Column int64_column(const std::string &name, const at::Tensor &v) {
 }
 
 // A running aggregate is null where its row's value is; a framed one where the frame holds fewer than
-// min_periods values, which a frame of a column without nulls can only do for min_periods > 1.
+// min_periods values, which a frame of a column without nulls can only do for min_periods > 1.  A
+// navigation function's output is always nullable (NTH_VALUE past the partition's end), except the
+// fill of a column without nulls, which is the column itself; a distribution function's never is.
 bool nullable_result(const WindowSpec &s, const Column &c) {
+  if (is_pick(s.func)) return true;
+  if (is_fill(s.func)) return c.nullable();
   if (s.func == WIN_CUMCOUNT || s.func == WIN_ROLLING_COUNT || s.func == WIN_RANGE_COUNT) return false;
   return c.nullable() || (is_framed(s.func) && s.min_periods > 1);
 }
@@ -192,9 +232,11 @@ TablePtr empty_result(const TablePtr &t, const std::vector<WindowSpec> &specs, c
   std::vector<Column> out = t->columns();
   for (size_t i = 0; i < specs.size(); ++i) {
     const WindowSpec &s = specs[i];
-    if (is_ranking(s.func)) {
+    if (is_ranking(s.func) || s.func == WIN_NTILE) {
       out.push_back(int64_column(ck.names[i], ex.empty_i64(0)));
-    } else if (is_shift(s.func)) {
+    } else if (is_dist(s.func)) {
+      out.push_back(make_fixed_column(ck.names[i], DataType(Type::DOUBLE), 0, ex.device, false));
+    } else if (is_shift(s.func) || is_pick(s.func) || is_fill(s.func)) {
       out.push_back(GatherColumn(t->column(s.col), ex.empty_i64(0)).with_name(ck.names[i]));
     } else {
       const Column &c = t->column(s.col);
@@ -257,9 +299,16 @@ TablePtr Window(const TablePtr &t, const std::vector<int> &partition_cols, const
   int64_t scans = 0;
 
   // ranking functions and LAG / LEAD: one scan of the flags
-  at::Tensor row_number, rank, dense_rank, phead;
-  bool framed = false;
+  at::Tensor row_number, rank, dense_rank, phead, qhead, rqhead;
+  bool framed = false, nav = false, nav_rtail = false, nav_rflags = false, percent_rank = false, cume_dist = false;
   for (const auto &s : specs) {
+    if (is_pick(s.func) || is_fill(s.func) || is_dist(s.func)) nav = true;
+    if (nav_needs_phead(s.func) && !phead.defined()) phead = ex.empty_i64(n);
+    if (nav_needs_rtail(s.func)) nav_rtail = true;
+    // the reversed fill scan restarts at the reversed flags
+    if (s.func == WIN_BFILL || (s.func == WIN_FIRST_VALUE && s.ignore_nulls)) nav_rflags = true;
+    if (s.func == WIN_PERCENT_RANK) percent_rank = true;
+    if (s.func == WIN_CUME_DIST) cume_dist = true;
     if (s.func == WIN_ROW_NUMBER && !row_number.defined()) row_number = ex.empty_i64(n);
     if (s.func == WIN_RANK && !rank.defined()) rank = ex.empty_i64(n);
     if (s.func == WIN_DENSE_RANK && !dense_rank.defined()) dense_rank = ex.empty_i64(n);
@@ -272,20 +321,33 @@ TablePtr Window(const TablePtr &t, const std::vector<int> &partition_cols, const
     KCALL(ex, window_carry, ptr<int64_t>(tagg), ptr<uint8_t>(tflag), ntiles, 3, kRank, step, ptr<int64_t>(carry));
     KCALL(ex, window_rank_apply, ptr<int64_t>(perm), ptr<uint8_t>(flags), n, ptr<int64_t>(carry),
           opt_ptr(row_number), opt_ptr(rank), opt_ptr(dense_rank), opt_ptr(phead));
+    if (percent_rank) {  // RANK - 1 = the head of the row's peers - phead
+      qhead = ex.empty_i64(n);
+      KCALL(ex, window_rank_heads, ptr<uint8_t>(flags), n, ptr<int64_t>(carry), nullptr, ptr<int64_t>(qhead));
+    }
     ++scans;
   }
 
-  // framed specs: the partition tails, as the heads of the reversed order
+  // framed specs, and the functions that look at the partition's end: the partition tails, as the
+  // heads of the reversed order.  CUME_DIST marks the peer tails in the same flags, and the scan's q word
+  // is then the last peer of every position.
   at::Tensor rflags, rtail;
-  if (framed) {
+  if (framed || nav_rtail || nav_rflags) {
     rflags = ex.empty_u8(n);
+    if (cume_dist) KCALL(ex, window_rev_peer_flags, ptr<uint8_t>(flags), n, ptr<uint8_t>(rflags));
+    else KCALL(ex, window_rev_flags, ptr<uint8_t>(flags), n, ptr<uint8_t>(rflags));
+  }
+  if (framed || nav_rtail) {
     rtail = ex.empty_i64(n);
     at::Tensor tagg = ex.empty_i64(3 * ntiles), tflag = ex.empty_u8(ntiles), carry = ex.empty_i64(3 * ntiles);
-    KCALL(ex, window_rev_flags, ptr<uint8_t>(flags), n, ptr<uint8_t>(rflags));
     KCALL(ex, window_rank_tile, ptr<uint8_t>(rflags), n, ptr<int64_t>(tagg), ptr<uint8_t>(tflag));
     KCALL(ex, window_carry, ptr<int64_t>(tagg), ptr<uint8_t>(tflag), ntiles, 3, kRank, step, ptr<int64_t>(carry));
     KCALL(ex, window_rank_apply, ptr<int64_t>(perm), ptr<uint8_t>(rflags), n, ptr<int64_t>(carry), nullptr, nullptr,
           nullptr, ptr<int64_t>(rtail));
+    if (cume_dist) {
+      rqhead = ex.empty_i64(n);
+      KCALL(ex, window_rank_heads, ptr<uint8_t>(rflags), n, ptr<int64_t>(carry), nullptr, ptr<int64_t>(rqhead));
+    }
     ++scans;
   }
   const int64_t lds_rows = KSIZE(ex, window_frame_lds_rows);
@@ -370,6 +432,27 @@ TablePtr Window(const TablePtr &t, const std::vector<int> &partition_cols, const
     return pyramids.emplace(std::make_pair(col, func), p).first->second;
   };
 
+  // fills: the tile pass and the carries once per (column, direction); pos = the fill position of
+  // every sorted position, which only the IGNORE NULLS forms ask for
+  struct Fill {
+    at::Tensor carry, pos;
+  };
+  std::map<std::pair<int, bool>, Fill> fills;
+  int64_t nav_gather = 0, nav_skipped = 0;
+  auto fill_of = [&](int col, bool rev) -> Fill & {
+    auto it = fills.find({col, rev});
+    if (it != fills.end()) return it->second;
+    const Dense &d = dense_of(col);
+    Fill f;
+    f.carry = ex.empty_i64(ntiles);
+    at::Tensor tagg = ex.empty_i64(ntiles), tflag = ex.empty_u8(ntiles);
+    KCALL(ex, window_fill_tile, rev ? ptr<uint8_t>(rflags) : ptr<uint8_t>(flags), n, rev, ptr<uint8_t>(d.valid),
+          ptr<int64_t>(tagg), ptr<uint8_t>(tflag));
+    KCALL(ex, window_carry, ptr<int64_t>(tagg), ptr<uint8_t>(tflag), ntiles, 1, kMax, step, ptr<int64_t>(f.carry));
+    ++scans;
+    return fills.emplace(std::make_pair(col, rev), f).first->second;
+  };
+
   std::vector<Column> out = t->columns();
   for (size_t i = 0; i < specs.size(); ++i) {
     const WindowSpec &s = specs[i];
@@ -378,7 +461,58 @@ TablePtr Window(const TablePtr &t, const std::vector<int> &partition_cols, const
       out.push_back(int64_column(name, s.func == WIN_ROW_NUMBER ? row_number : s.func == WIN_RANK ? rank : dense_rank));
       continue;
     }
+    if (is_dist(s.func)) {
+      Column col = make_fixed_column(name, DataType(s.func == WIN_NTILE ? Type::INT64 : Type::DOUBLE), n, ex.device,
+                                     false);
+      KCALL(ex, window_dist_apply, ptr<int64_t>(perm), ptr<int64_t>(phead), ptr<int64_t>(rtail), opt_ptr(qhead),
+            opt_ptr(rqhead), n, s.func - WIN_NTILE, s.arg, reinterpret_cast<uint8_t *>(col.data.data_ptr()));
+      out.push_back(std::move(col));
+      continue;
+    }
     const Column &c = t->column(s.col);
+    if (is_fill(s.func) || is_pick(s.func)) {
+      if (is_fill(s.func) && !c.nullable()) {  // nothing to fill: the column itself, no scan
+        out.push_back(c.with_name(name));
+        ++nav_skipped;
+        continue;
+      }
+      const bool value = nav_value_mode(c);
+      const bool rev = s.func == WIN_BFILL || s.func == WIN_FIRST_VALUE;
+      // the IGNORE NULLS forms of a column without nulls are the plain ones
+      const bool scan = is_fill(s.func) || (s.ignore_nulls && c.nullable());
+      const ColView cv = c.view();
+      Column col;
+      at::Tensor src;
+      if (value) col = make_fixed_column(name, c.type, n, ex.device, true);
+      else src = ex.empty_i64(n);
+      uint8_t *o = value ? reinterpret_cast<uint8_t *>(col.data.data_ptr()) : nullptr;
+      uint8_t *ov = value ? col.validity.data_ptr<uint8_t>() : nullptr;
+      const Dense *d = (value || scan) ? &dense_of(s.col) : nullptr;
+      const uint64_t *bits = d != nullptr ? u64(d->bits) : nullptr;
+      const uint8_t *valid = d != nullptr && d->valid.defined() ? ptr<uint8_t>(d->valid) : nullptr;
+      const uint8_t *restarts = !scan ? nullptr : rev ? ptr<uint8_t>(rflags) : ptr<uint8_t>(flags);
+      Fill *f = scan ? &fill_of(s.col, rev) : nullptr;
+      if (is_fill(s.func)) {
+        KCALL(ex, window_fill_apply, cv, ptr<int64_t>(perm), restarts, n, rev, s.limit, bits, valid,
+              ptr<int64_t>(f->carry), o, ov, opt_ptr(src), nullptr);
+      } else {
+        if (f != nullptr && !f->pos.defined()) {
+          f->pos = ex.empty_i64(n);
+          KCALL(ex, window_fill_apply, cv, ptr<int64_t>(perm), restarts, n, rev, 0, bits, valid,
+                ptr<int64_t>(f->carry), nullptr, nullptr, nullptr, ptr<int64_t>(f->pos));
+        }
+        const int form = s.func == WIN_NTH_VALUE ? 2 : (s.func == WIN_FIRST_VALUE ? 0 : 1) + (f != nullptr ? 3 : 0);
+        KCALL(ex, window_nav_pick, cv, ptr<int64_t>(perm), opt_ptr(phead), opt_ptr(rtail),
+              f != nullptr ? ptr<int64_t>(f->pos) : nullptr, n, form, s.arg, bits, valid, o, ov, opt_ptr(src));
+      }
+      if (value) {
+        out.push_back(std::move(col));
+      } else {
+        out.push_back(GatherColumn(c, src).with_name(name));
+        ++nav_gather;
+      }
+      continue;
+    }
     if (is_shift(s.func)) {
       const int64_t off = std::min(s.arg, n);  // n rows away is outside every partition
       at::Tensor src = ex.empty_i64(n);
@@ -478,6 +612,11 @@ TablePtr Window(const TablePtr &t, const std::vector<int> &partition_cols, const
   }
   trace::add_counter("window.scan", scans);
   trace::add_counter("window.tiles", scans * ntiles);
+  if (nav) {
+    trace::add_counter("window.nav.fill", (int64_t)fills.size());
+    trace::add_counter("window.nav.gather", nav_gather);
+    trace::add_counter("window.nav.skipped", nav_skipped);
+  }
   if (frames_lds) trace::add_counter("window.frame.lds", frames_lds);
   if (frames_wide) trace::add_counter("window.frame.wide", frames_wide);
   if (range_specs) {

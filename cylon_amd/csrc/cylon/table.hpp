@@ -88,7 +88,10 @@ struct SortOptions {
 // Window functions (docs/semantics.md "Window functions"), numbered as the C ABI and the bindings
 // pass them.  Functions 0 .. 8 have the frame ROWS BETWEEN UNBOUNDED PRECEDING AND CURRENT ROW; the
 // ROLLING functions have ROWS BETWEEN preceding PRECEDING AND following FOLLOWING, the RANGE functions
-// RANGE BETWEEN preceding PRECEDING AND following FOLLOWING over the one order column.
+// RANGE BETWEEN preceding PRECEDING AND following FOLLOWING over the one order column.  The navigation
+// functions 19 .. 21 have the whole partition as their frame (not SQL's default frame), FFILL / BFILL
+// read back / ahead inside the partition, and the distribution functions 24 .. 26 need no column
+// (docs/semantics.md "Navigation and distribution functions").
 enum WindowFunc : int {
   WIN_ROW_NUMBER = 0,
   WIN_RANK = 1,
@@ -109,15 +112,23 @@ enum WindowFunc : int {
   WIN_RANGE_MEAN = 16,
   WIN_RANGE_MIN = 17,
   WIN_RANGE_MAX = 18,
+  WIN_FIRST_VALUE = 19,
+  WIN_LAST_VALUE = 20,
+  WIN_NTH_VALUE = 21,
+  WIN_FFILL = 22,
+  WIN_BFILL = 23,
+  WIN_NTILE = 24,
+  WIN_PERCENT_RANK = 25,
+  WIN_CUME_DIST = 26,
 };
 
 constexpr int64_t kWindowUnbounded = INT64_MAX;  // a RANGE offset: no bound on that side
 
 struct WindowSpec {
   WindowFunc func;
-  int col;           // value column; ignored by the three ranking functions
-  int64_t arg;       // LAG / LEAD: the offset (>= 0)
-  std::string name;  // output column; empty: <func>_<column name>, or the bare ranking function
+  int col;           // value column; ignored by the ranking and the distribution functions
+  int64_t arg;       // LAG / LEAD: the offset (>= 0); NTH_VALUE, NTILE: k (>= 1)
+  std::string name;  // output column; empty: <func>_<column name>, or the bare function without a column
   // ROLLING functions: rows of the partition before and after the current one (>= 0; >= the table's
   // rows: unbounded), and the non-null values below which the result is null (>= 1)
   int64_t preceding = 0;
@@ -129,6 +140,11 @@ struct WindowSpec {
   double preceding_f = 0;
   double following_f = 0;
   bool offset_is_float = false;
+  // FIRST_VALUE / LAST_VALUE: the first / last non-null cell of the partition instead of the cell of
+  // its first / last row (Invalid on NTH_VALUE)
+  bool ignore_nulls = false;
+  // FFILL / BFILL: at most this many consecutive nulls after / before a value are filled (>= 0; 0: all)
+  int64_t limit = 0;
 };
 
 // As-of join (docs/semantics.md "As-of join"): every left row with the nearest right row of its group

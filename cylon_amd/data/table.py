@@ -377,6 +377,9 @@ class Table(PandasOpsMixin):
                       "rolling_max": 13}
     # RANGE frames: they go through C.window_range_frames
     _RANGE_FUNCS = {"range_count": 14, "range_sum": 15, "range_mean": 16, "range_min": 17, "range_max": 18}
+    # navigation and distribution functions: they go through C.window_nav
+    _NAV_FUNCS = {"first_value": 19, "last_value": 20, "nth_value": 21, "ffill": 22, "bfill": 23, "ntile": 24,
+                  "percent_rank": 25, "cume_dist": 26}
     _UNBOUNDED = (1 << 63) - 1
 
     @classmethod
@@ -388,6 +391,11 @@ class Table(PandasOpsMixin):
     def _is_range(cls, spec):
         return (not isinstance(spec, str) and len(spec) > 0 and isinstance(spec[0], str)
                 and spec[0].lower() in cls._RANGE_FUNCS)
+
+    @classmethod
+    def _is_nav(cls, spec):
+        fn = spec if isinstance(spec, str) else (spec[0] if len(spec) > 0 else None)
+        return isinstance(fn, str) and fn.lower() in cls._NAV_FUNCS
 
     def _window_keys(self, partition_by, order_by, ascending):
         part = self._resolve_columns(partition_by) if partition_by is not None else []
@@ -439,6 +447,46 @@ class Table(PandasOpsMixin):
         floats = [float(b) if is_float and b is not None else 0.0 for b in spec[2:4]]
         return (self._RANGE_FUNCS[fn], self._resolve_column(spec[1]), ints[0], ints[1], floats[0], floats[1], is_float,
                 int(spec[4]) if len(spec) == 5 else 1)
+
+    def _nav_spec(self, spec):
+        """(WindowFunc number, value column, k, ignore_nulls, limit) of a navigation or distribution spec;
+        k < 1, a negative limit and ignore_nulls on nth_value are the engine's to refuse"""
+        spec = (spec,) if isinstance(spec, str) else tuple(spec)
+        fn = spec[0].lower()
+        fid = self._NAV_FUNCS[fn]
+        if fid >= 25:
+            if len(spec) != 1:
+                raise ValueError(f"window function {fn} takes no argument")
+            return fid, -1, 0, False, 0
+        if fid == 24:
+            if len(spec) != 2:
+                raise ValueError(f"window spec {spec!r}: expected ('ntile', k)")
+            return fid, -1, int(spec[1]), False, 0
+        if fid == 21:
+            if len(spec) < 3 or len(spec) > 4:
+                raise ValueError(f"window spec {spec!r}: expected ('nth_value', column, k)")
+            return fid, self._resolve_column(spec[1]), int(spec[2]), bool(spec[3]) if len(spec) == 4 else False, 0
+        if len(spec) < 2 or len(spec) > 3:
+            raise ValueError(f"window spec {spec!r}: expected ({fn!r}, column"
+                             + ("[, ignore_nulls])" if fid <= 20 else "[, limit])"))
+        opt = spec[2] if len(spec) == 3 else None
+        if fid <= 20:
+            return fid, self._resolve_column(spec[1]), 0, bool(opt), 0
+        return fid, self._resolve_column(spec[1]), 0, False, 0 if opt is None else int(opt)
+
+    def _window_nav_args(self, partition_by, order_by, ascending, funcs):
+        """_window_range_args plus ignore_nulls and limit, for a call with at least one navigation or
+        distribution spec"""
+        plain = {n: ("row_number" if self._is_nav(s) else s) for n, s in (funcs or {}).items()}
+        part, order, asc, *lists = self._window_range_args(partition_by, order_by, ascending, plain)
+        ignore, limit = [], []
+        for i, spec in enumerate((funcs or {}).values()):
+            fid, col, k, ign, lim = self._nav_spec(spec) if self._is_nav(spec) else (lists[0][i], lists[1][i],
+                                                                                     lists[2][i], False, 0)
+            lists[0][i], lists[1][i], lists[2][i] = fid, col, k
+            ignore.append(ign)
+            limit.append(lim)
+        return (part, order, asc, *lists, ignore, limit)
 
     def _window_range_args(self, partition_by, order_by, ascending, funcs):
         """_window_frame_args plus the float offsets, for a call with at least one range spec"""
@@ -504,7 +552,23 @@ class Table(PandasOpsMixin):
         temporal type (offsets in its unit) or float32 / float64; offsets are ints, floats (float
         columns only) or None = unbounded, e.g. ("range_mean", "v", 5_000_000_000, 0) over a
         timestamp[ns] column for the mean of the last 5 seconds (pandas rolling('5s', closed='both')
-        on unique timestamps).  Everything else is as for the rolling aggregates."""
+        on unique timestamps).  Everything else is as for the rolling aggregates.
+
+        Navigation functions read one cell of the partition, whatever the column's type:
+        ("first_value" | "last_value", column[, ignore_nulls = False]) the cell of the partition's first /
+        last row in window order -- the frame is the WHOLE partition, not SQL's default frame, under which
+        last_value would be the row's last peer -- or, with ignore_nulls, its first / last non-null cell;
+        ("nth_value", column, k) the cell of its k-th row (k >= 1), null in a shorter partition;
+        ("ffill" | "bfill", column[, limit = None]) the cell itself, or for a null cell the nearest
+        non-null one before / after it in the partition, at most `limit` positions away (the pandas
+        groupby().ffill(limit=)).  Null is the validity byte: NaN is a value, it is copied and it stops a
+        fill.  Distribution functions take no column: ("ntile", k) the bucket 1 .. k of the row when the
+        partition is cut into k runs whose sizes differ by at most one (the larger first),
+        "percent_rank" = (rank - 1) / (rows - 1), 0.0 in a one-row partition, and "cume_dist" = the rows
+        at or before the row's last peer / rows (docs/semantics.md "Navigation and distribution
+        functions")."""
+        if any(self._is_nav(s) for s in (funcs or {}).values()):
+            return self._wrap(C.window_nav(self._t, *self._window_nav_args(partition_by, order_by, ascending, funcs)))
         if any(self._is_range(s) for s in (funcs or {}).values()):
             return self._wrap(C.window_range_frames(self._t, *self._window_range_args(partition_by, order_by,
                                                                                        ascending, funcs)))
@@ -516,7 +580,11 @@ class Table(PandasOpsMixin):
     def distributed_window(self, partition_by=None, order_by=None, ascending: Union[bool, List[bool]] = True,
                            funcs: dict = None) -> "Table":
         """window() after a shuffle by the partition columns (at least one when the world is larger than
-        1); the output row order is unspecified.  Rolling and range specs as in window()."""
+        1); the output row order is unspecified.  Rolling, range, navigation and distribution specs as in
+        window()."""
+        if any(self._is_nav(s) for s in (funcs or {}).values()):
+            return self._wrap(C.distributed_window_nav(
+                self._t, *self._window_nav_args(partition_by, order_by, ascending, funcs)))
         if any(self._is_range(s) for s in (funcs or {}).values()):
             return self._wrap(C.distributed_window_range_frames(
                 self._t, *self._window_range_args(partition_by, order_by, ascending, funcs)))
@@ -524,6 +592,38 @@ class Table(PandasOpsMixin):
             return self._wrap(C.distributed_window_frames(
                 self._t, *self._window_frame_args(partition_by, order_by, ascending, funcs)))
         return self._wrap(C.distributed_window(self._t, *self._window_args(partition_by, order_by, ascending, funcs)))
+
+    def _fill(self, fn, by, order_by, ascending, limit, columns):
+        part = self._resolve_columns(by) if by is not None else []
+        order = self._resolve_columns(order_by) if order_by is not None else []
+        if limit is not None and int(limit) <= 0:
+            raise ValueError("limit must be greater than 0")
+        keys = set(part) | set(order)
+        cols = self._resolve_columns(columns) if columns is not None else \
+            [c for c in range(self.column_count) if c not in keys]
+        if not cols:
+            return self
+        names = self.column_names
+        tmp = [f"__{fn}_{i}__" for i in range(len(cols))]
+        w = self.window(part or None, order or None, ascending,
+                        {t: (fn, c) if limit is None else (fn, c, int(limit)) for t, c in zip(tmp, cols)})
+        filled = dict(zip(cols, range(self.column_count, self.column_count + len(cols))))
+        out = w.project([filled.get(c, c) for c in range(self.column_count)])
+        out.rename(names)
+        return out
+
+    def ffill(self, by=None, order_by=None, limit=None, columns=None,
+              ascending: Union[bool, List[bool]] = True) -> "Table":
+        """Forward fill (the pandas groupby(by).ffill(limit=)): the named columns -- by default every column
+        that is neither a `by` nor an `order_by` column -- with each null cell replaced by the nearest
+        non-null cell before it in its `by` group, in `order_by` order (neither given: input row order), at
+        most `limit` positions back.  Rows, column order and names stay.  NaN is a value, not a null."""
+        return self._fill("ffill", by, order_by, ascending, limit, columns)
+
+    def bfill(self, by=None, order_by=None, limit=None, columns=None,
+              ascending: Union[bool, List[bool]] = True) -> "Table":
+        """Backward fill: ffill with the nearest non-null cell after the row."""
+        return self._fill("bfill", by, order_by, ascending, limit, columns)
 
     _ASOF_DIRECTIONS = {"backward": 0, "forward": 1, "nearest": 2}
 

@@ -409,11 +409,30 @@ class DataFrame(object):
         aggregates over a ROWS frame, e.g. {"avg7": ("rolling_mean", "amount", 6, 0)} (the pandas
         groupby().rolling(7, min_periods=1).mean()), or over a RANGE frame of the order column's values, e.g.
         {"sum5s": ("range_sum", "amount", 5_000_000_000, 0)} ordered by a timestamp[ns] column (the pandas
-        rolling('5s', closed='both') on unique timestamps); a bound of None is unbounded.  With an env
+        rolling('5s', closed='both') on unique timestamps); a bound of None is unbounded.  Navigation and
+        distribution functions: ("first_value" | "last_value", column[, ignore_nulls]) over the whole
+        partition, ("nth_value", column, k), ("ffill" | "bfill", column[, limit]), ("ntile", k),
+        "percent_rank" and "cume_dist".  With an env
         of more than one rank the rows are first shuffled by the partition columns."""
         if env is None or env.world_size <= 1:
             return DataFrame(self._table.window(partition_by, order_by, ascending, funcs))
         return DataFrame(self._change_context(env)._table.distributed_window(partition_by, order_by, ascending, funcs))
+
+    def _fill(self, fn, by, order_by, limit, columns, env) -> "DataFrame":
+        if env is None or env.world_size <= 1:
+            return DataFrame(getattr(self._table, fn)(by=by, order_by=order_by, limit=limit, columns=columns))
+        raise NotImplementedError(f"{fn} with an env of more than one rank: use window(funcs=..., env=env)")
+
+    def ffill(self, by=None, order_by=None, limit=None, columns=None, env: CylonEnv = None) -> "DataFrame":
+        """Forward fill (the pandas groupby(by).ffill(limit=)): the named columns, by default every column
+        that is not a key, with each null cell replaced by the nearest non-null cell before it in its `by`
+        group in `order_by` order (neither given: input row order), at most `limit` positions back.
+        Column order and names are kept.  Unlike pandas, NaN is a value: it is copied and stops a fill."""
+        return self._fill("ffill", by, order_by, limit, columns, env)
+
+    def bfill(self, by=None, order_by=None, limit=None, columns=None, env: CylonEnv = None) -> "DataFrame":
+        """Backward fill: ffill with the nearest non-null cell after the row."""
+        return self._fill("bfill", by, order_by, limit, columns, env)
 
     def merge_asof(self, right: "DataFrame", on=None, left_on=None, right_on=None, by=None, left_by=None,
                    right_by=None, suffixes=("_x", "_y"), tolerance=None, allow_exact_matches: bool = True,

@@ -81,6 +81,21 @@ int cylon_window_range_frames(const char *table_id, const int32_t *partition_col
                               const int64_t *preceding, const int64_t *following, const double *preceding_f,
                               const double *following_f, const int32_t *offset_is_float, const int64_t *min_periods,
                               const char *const *names, int nspecs, int distributed, const char *dest_id);
+/* cylon_window_range_frames with the navigation and distribution functions too: also funcs[i] =
+   19 FIRST_VALUE, 20 LAST_VALUE, 21 NTH_VALUE (the cell of the partition's first / last / spec_args[i]-th
+   row in window order; the frame is the whole partition, not SQL's default frame; NTH_VALUE is null in
+   a shorter partition), 22 FFILL, 23 BFILL (a null cell takes the nearest non-null cell before / after
+   it in its partition, at most limit[i] positions away; 0: no limit), 24 NTILE (spec_args[i] buckets,
+   int64), 25 PERCENT_RANK, 26 CUME_DIST (float64); 24..26 ignore spec_columns.  ignore_nulls[i] != 0
+   makes FIRST_VALUE / LAST_VALUE the partition's first / last non-null cell (Invalid on NTH_VALUE).  Null
+   is the validity byte: NaN is a value.  ignore_nulls / limit may be NULL (false, 0). */
+int cylon_window_nav(const char *table_id, const int32_t *partition_columns, int npartition,
+                     const int32_t *order_columns, const int32_t *ascending, int norder, const int32_t *funcs,
+                     const int32_t *spec_columns, const int64_t *spec_args, const int64_t *preceding,
+                     const int64_t *following, const double *preceding_f, const double *following_f,
+                     const int32_t *offset_is_float, const int64_t *min_periods, const int32_t *ignore_nulls,
+                     const int64_t *limit, const char *const *names, int nspecs, int distributed,
+                     const char *dest_id);
 /* as-of join: every row of the left table, in its row order, with the columns of the nearest right row
    whose `by` columns equal its own (nby may be 0) -- direction 0 BACKWARD: the last right_on <=
    left_on, 1 FORWARD: the first right_on >= left_on, 2 NEAREST: the nearer of the two, the backward

@@ -64,7 +64,9 @@ def window(t: Table, partition_by=None, order_by=None, ascending: Union[bool, Li
     """Table.window: ranking, running aggregates, lag / lead and rolling aggregates over a ROWS frame,
     ("rolling_sum" | "rolling_mean" | "rolling_min" | "rolling_max" | "rolling_count", column, preceding,
     following[, min_periods]), or over a RANGE frame of the one order column's values, ("range_sum" | ... |
-    "range_count", column, preceding, following[, min_periods])."""
+    "range_count", column, preceding, following[, min_periods]), and the navigation and distribution
+    functions ("first_value" | "last_value", column[, ignore_nulls]), ("nth_value", column, k), ("ffill" |
+    "bfill", column[, limit]), ("ntile", k), "percent_rank", "cume_dist"."""
     return t.window(partition_by, order_by, ascending, funcs)
 
 
