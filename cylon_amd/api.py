@@ -64,6 +64,10 @@ def capi_library() -> ctypes.CDLL:
                               pp(ctypes.c_int32), pp(ctypes.c_int32), pp(i64), pp(i64), pp(i64),
                               pp(ctypes.c_double), pp(ctypes.c_double), pp(ctypes.c_int32), pp(i64),
                               pp(ctypes.c_int32), pp(i64), pp(s), i, i, s], i),
+        "cylon_window_moment_frames": ([s, pp(ctypes.c_int32), i, pp(ctypes.c_int32), pp(ctypes.c_int32), i,
+                                        pp(ctypes.c_int32), pp(ctypes.c_int32), pp(i64), pp(i64), pp(i64),
+                                        pp(ctypes.c_double), pp(ctypes.c_double), pp(ctypes.c_int32), pp(i64),
+                                        pp(ctypes.c_int32), pp(i64), pp(ctypes.c_int32), pp(s), i, i, s], i),
         "cylon_asof_join": ([s, s, i, i, pp(ctypes.c_int32), pp(ctypes.c_int32), i, i, i, i, i64, ctypes.c_double, s, s,
                              s, i], i),
         "cylon_interval_join": ([s, s, i, i, i, pp(ctypes.c_int32), pp(ctypes.c_int32), i, i, i, s, s, s, i], i),

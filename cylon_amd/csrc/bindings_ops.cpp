@@ -484,6 +484,69 @@ void register_extended_ops(py::module &m) {
       py::arg("cols"), py::arg("args"), py::arg("names"), py::arg("preceding"), py::arg("following"),
       py::arg("preceding_f"), py::arg("following_f"), py::arg("offset_is_float"), py::arg("min_periods"),
       py::arg("ignore_nulls"), py::arg("limit"), rel);
+  // the same with VAR / STD over ROWS and RANGE frames too (functions 0 .. 30): ddof[i] for functions
+  // 27 .. 30, which read their frame as ROLLING_MEAN resp. RANGE_MEAN do
+  auto moment_specs = [nav_specs](const std::vector<int> &funcs, const std::vector<int> &cols,
+                                  const std::vector<int64_t> &args, const std::vector<std::string> &names,
+                                  const std::vector<int64_t> &preceding, const std::vector<int64_t> &following,
+                                  const std::vector<double> &preceding_f, const std::vector<double> &following_f,
+                                  const std::vector<bool> &offset_is_float, const std::vector<int64_t> &min_periods,
+                                  const std::vector<bool> &ignore_nulls, const std::vector<int64_t> &limit,
+                                  const std::vector<int> &ddof) {
+    const size_t k = funcs.size();
+    CYLON_CHECK(ddof.size() == k, Code::Invalid, "window spec lists differ in length");
+    std::vector<int> known = funcs;  // nav_specs checks the other lists and knows functions 0 .. 26
+    for (size_t i = 0; i < k; ++i) {
+      CYLON_CHECK(funcs[i] >= WIN_ROW_NUMBER && funcs[i] <= WIN_RANGE_STD, Code::Invalid,
+                  "window function " << funcs[i]);
+      if (funcs[i] > WIN_CUME_DIST) known[i] = WIN_ROW_NUMBER;
+    }
+    std::vector<WindowSpec> specs = nav_specs(known, cols, args, names, preceding, following, preceding_f,
+                                              following_f, offset_is_float, min_periods, ignore_nulls, limit);
+    for (size_t i = 0; i < k; ++i) {
+      specs[i].func = static_cast<WindowFunc>(funcs[i]);
+      specs[i].ddof = ddof[i];
+    }
+    return specs;
+  };
+  m.def(
+      "window_moment_frames",
+      [moment_specs](const TablePtr &t, const std::vector<int> &part, const std::vector<int> &order,
+                     const std::vector<bool> &asc, const std::vector<int> &funcs, const std::vector<int> &cols,
+                     const std::vector<int64_t> &args, const std::vector<std::string> &names,
+                     const std::vector<int64_t> &preceding, const std::vector<int64_t> &following,
+                     const std::vector<double> &preceding_f, const std::vector<double> &following_f,
+                     const std::vector<bool> &offset_is_float, const std::vector<int64_t> &min_periods,
+                     const std::vector<bool> &ignore_nulls, const std::vector<int64_t> &limit,
+                     const std::vector<int> &ddof, int64_t carry_step_tiles) {
+        return ops::Window(t, part, order, asc,
+                           moment_specs(funcs, cols, args, names, preceding, following, preceding_f, following_f,
+                                        offset_is_float, min_periods, ignore_nulls, limit, ddof),
+                           carry_step_tiles);
+      },
+      py::arg("table"), py::arg("partition_cols"), py::arg("order_cols"), py::arg("ascending"), py::arg("funcs"),
+      py::arg("cols"), py::arg("args"), py::arg("names"), py::arg("preceding"), py::arg("following"),
+      py::arg("preceding_f"), py::arg("following_f"), py::arg("offset_is_float"), py::arg("min_periods"),
+      py::arg("ignore_nulls"), py::arg("limit"), py::arg("ddof"), py::arg("carry_step_tiles") = 0, rel);
+  m.def(
+      "distributed_window_moment_frames",
+      [moment_specs](const TablePtr &t, const std::vector<int> &part, const std::vector<int> &order,
+                     const std::vector<bool> &asc, const std::vector<int> &funcs, const std::vector<int> &cols,
+                     const std::vector<int64_t> &args, const std::vector<std::string> &names,
+                     const std::vector<int64_t> &preceding, const std::vector<int64_t> &following,
+                     const std::vector<double> &preceding_f, const std::vector<double> &following_f,
+                     const std::vector<bool> &offset_is_float, const std::vector<int64_t> &min_periods,
+                     const std::vector<bool> &ignore_nulls, const std::vector<int64_t> &limit,
+                     const std::vector<int> &ddof) {
+        return ops::DistributedWindow(t, part, order, asc,
+                                      moment_specs(funcs, cols, args, names, preceding, following, preceding_f,
+                                                   following_f, offset_is_float, min_periods, ignore_nulls, limit,
+                                                   ddof));
+      },
+      py::arg("table"), py::arg("partition_cols"), py::arg("order_cols"), py::arg("ascending"), py::arg("funcs"),
+      py::arg("cols"), py::arg("args"), py::arg("names"), py::arg("preceding"), py::arg("following"),
+      py::arg("preceding_f"), py::arg("following_f"), py::arg("offset_is_float"), py::arg("min_periods"),
+      py::arg("ignore_nulls"), py::arg("limit"), py::arg("ddof"), rel);
   // as-of join: tolerance = None, an int (integer / temporal `on`) or a float (float `on`)
   auto asof_options = [](int direction, bool allow_exact, const py::object &tolerance, const std::string &left_prefix,
                          const std::string &right_prefix) {

@@ -258,6 +258,33 @@ CYLON_CAPI int cylon_window_nav(const char *id, const int32_t *partition_cols, i
   });
 }
 
+CYLON_CAPI int cylon_window_moment_frames(const char *id, const int32_t *partition_cols, int npartition,
+                                          const int32_t *order_cols, const int32_t *ascending, int norder,
+                                          const int32_t *funcs, const int32_t *spec_cols, const int64_t *spec_args,
+                                          const int64_t *preceding, const int64_t *following,
+                                          const double *preceding_f, const double *following_f,
+                                          const int32_t *offset_is_float, const int64_t *min_periods,
+                                          const int32_t *ignore_nulls, const int64_t *limit, const int32_t *ddof,
+                                          const char *const *names, int nspecs, int distributed, const char *dest) {
+  return guard([&] {
+    std::vector<bool> dirs;
+    for (int i = 0; i < norder; ++i) dirs.push_back(ascending == nullptr || ascending[i] != 0);
+    std::vector<WindowSpec> specs;
+    for (int i = 0; i < nspecs; ++i) {
+      if (funcs[i] < WIN_ROW_NUMBER || funcs[i] > WIN_RANGE_STD)
+        return status(Status(Code::Invalid, "window function " + std::to_string(funcs[i])));
+      specs.push_back({static_cast<WindowFunc>(funcs[i]), spec_cols ? spec_cols[i] : -1, spec_args ? spec_args[i] : 0,
+                       names && names[i] ? names[i] : "", preceding ? preceding[i] : 0, following ? following[i] : 0,
+                       min_periods ? min_periods[i] : 1, preceding_f ? preceding_f[i] : 0.0,
+                       following_f ? following_f[i] : 0.0, offset_is_float != nullptr && offset_is_float[i] != 0,
+                       ignore_nulls != nullptr && ignore_nulls[i] != 0, limit ? limit[i] : 0, ddof ? ddof[i] : 1});
+    }
+    return status(WindowTable(id, std::vector<int32_t>(partition_cols, partition_cols + npartition),
+                              std::vector<int32_t>(order_cols, order_cols + norder), dirs, specs, dest,
+                              distributed != 0));
+  });
+}
+
 CYLON_CAPI int cylon_asof_join(const char *left_id, const char *right_id, int left_on, int right_on,
                                const int32_t *left_by, const int32_t *right_by, int nby, int direction, int allow_exact,
                                int has_tolerance, int64_t tolerance_i, double tolerance_f, const char *left_prefix,

@@ -607,6 +607,29 @@ void frame_range_apply(const ColView &col, const int64_t *perm, int64_t n, int f
                        const uint64_t *P, const uint64_t *S, const uint64_t *E, const uint64_t *cP,
                        const uint64_t *cS, const uint64_t *cE, uint8_t *out, uint8_t *out_valid, void *stream);
 
+/* frame_moments.hip (CPU twin cpu_frame_moments.cpp): VAR / STD over the ROWS or RANGE frame of sorted
+   position i (docs/semantics.md "Framed aggregates", VAR / STD).  Shared rules:
+   frame_moments_common.hpp.
+     frame_moments_pyramid  the moment pyramid of one value column: frame_range_pyramid's geometry with
+                            the state (count, mean, M2) of the non-null values, each converted to
+                            float64, merged by fm_merge.  P, S: fm_words(fm_ps_slots(n)) 64-bit words
+                            each, E: fm_words(fm_e_slots(n)), three planes per buffer.  Nothing to do
+                            for n <= 8.
+     frame_moments_apply    out[perm[i]] (float64) = M2 / (m - ddof) of the frame's state read off the
+                            pyramid, or its square root (std_dev); out_valid[perm[i]] = m >= min_periods
+                            and m - ddof > 0.  The frame: lo / hi of frame_range_bounds when they are
+                            not nullptr (a RANGE spec), else max(i - preceding, phead[i]) ..
+                            min(i + following, tail(i)) (a ROWS spec; rtail as rolling_lds takes it;
+                            preceding, following >= 0 of any size).  ddof >= 0, min_periods >= 1.
+   n < 2^32. */
+void frame_moments_pyramid(const ColView &col, int64_t n, const uint64_t *dense, const uint8_t *dense_valid,
+                           uint64_t *P, uint64_t *S, uint64_t *E, void *stream);
+void frame_moments_apply(const ColView &col, const int64_t *perm, int64_t n, bool std_dev, int64_t ddof,
+                         int64_t min_periods, const uint64_t *dense, const uint8_t *dense_valid, const uint32_t *lo,
+                         const uint32_t *hi, const int64_t *phead, const int64_t *rtail, int64_t preceding,
+                         int64_t following, const uint64_t *P, const uint64_t *S, const uint64_t *E, uint8_t *out,
+                         uint8_t *out_valid, void *stream);
+
 /* window_nav.hip (CPU twin cpu_window_nav.cpp): FIRST / LAST / NTH_VALUE, FFILL / BFILL, NTILE,
    PERCENT_RANK and CUME_DIST (docs/semantics.md "Navigation and distribution functions") from what the
    window operator already has: perm, the flags, the dense values and validity bytes of window_tile,

@@ -324,6 +324,7 @@ void preload_asof();
 void preload_bitmap();
 void preload_copy();
 void preload_delay();
+void preload_frame_moments();
 void preload_frame_range();
 void preload_groupby();
 void preload_hash_join();
@@ -355,6 +356,7 @@ void preload_device_code() {
   preload_bitmap();
   preload_copy();
   preload_delay();
+  preload_frame_moments();
   preload_frame_range();
   preload_groupby();
   preload_hash_join();

@@ -26,11 +26,17 @@
 // phead / rtail, the distribution functions one over phead, rtail and the peer heads / tails that the
 // two rank scans carry anyway.  Columns of width 1, 2, 4 or 8 are written straight from the dense
 // values (value mode); every other type goes through a source-row array and GatherColumn.
+//
+// A VAR / STD spec over a ROWS or a RANGE frame (kernels/frame_moments.hip) shares all of that again.  Every
+// value column gets one moment pyramid of (count, mean, M2) states per call, whatever the number of specs,
+// their frame kinds, offsets, ddof or min_periods; a RANGE spec reuses the bounds search of its
+// (preceding, following), a ROWS spec computes its bounds from phead / rtail in the query launch.
 #include <algorithm>
 #include <map>
 #include <set>
 #include <tuple>
 
+#include "../kernels/frame_moments_common.hpp"
 #include "../kernels/frame_range_common.hpp"
 
 #include "../trace.hpp"
@@ -73,6 +79,10 @@ const char *func_name(WindowFunc f) {
     case WIN_NTILE: return "ntile";
     case WIN_PERCENT_RANK: return "percent_rank";
     case WIN_CUME_DIST: return "cume_dist";
+    case WIN_ROLLING_VAR: return "rolling_var";
+    case WIN_ROLLING_STD: return "rolling_std";
+    case WIN_RANGE_VAR: return "range_var";
+    case WIN_RANGE_STD: return "range_std";
   }
   CYLON_THROW(Code::Invalid, "window function " << static_cast<int>(f));
 }
@@ -81,7 +91,11 @@ bool is_ranking(WindowFunc f) { return f == WIN_ROW_NUMBER || f == WIN_RANK || f
 bool is_shift(WindowFunc f) { return f == WIN_LAG || f == WIN_LEAD; }
 bool is_rolling(WindowFunc f) { return f >= WIN_ROLLING_COUNT && f <= WIN_ROLLING_MAX; }
 bool is_range(WindowFunc f) { return f >= WIN_RANGE_COUNT && f <= WIN_RANGE_MAX; }
-bool is_framed(WindowFunc f) { return is_rolling(f) || is_range(f); }
+// VAR / STD over a ROWS resp. a RANGE frame
+bool is_moment_rolling(WindowFunc f) { return f == WIN_ROLLING_VAR || f == WIN_ROLLING_STD; }
+bool is_moment_range(WindowFunc f) { return f == WIN_RANGE_VAR || f == WIN_RANGE_STD; }
+bool is_moment(WindowFunc f) { return is_moment_rolling(f) || is_moment_range(f); }
+bool is_framed(WindowFunc f) { return is_rolling(f) || is_range(f) || is_moment(f); }
 bool is_pick(WindowFunc f) { return f >= WIN_FIRST_VALUE && f <= WIN_NTH_VALUE; }
 bool is_fill(WindowFunc f) { return f == WIN_FFILL || f == WIN_BFILL; }
 bool is_dist(WindowFunc f) { return f >= WIN_NTILE && f <= WIN_CUME_DIST; }
@@ -129,6 +143,10 @@ std::pair<int, DataType> value_plan(const WindowSpec &s, const Column &c) {
     case WIN_CUMCOUNT:
     case WIN_ROLLING_COUNT: return {kCount, DataType(Type::INT64)};
     case WIN_ROLLING_MEAN: return {c.type.kind() == ValueKind::FLOAT ? kSumF : kSumI, DataType(Type::DOUBLE)};
+    case WIN_ROLLING_VAR:
+    case WIN_ROLLING_STD:
+    case WIN_RANGE_VAR:
+    case WIN_RANGE_STD: return {kCount, DataType(Type::DOUBLE)};  // the moment kernels take no function
     case WIN_ROLLING_SUM:
     case WIN_CUMSUM: return {c.type.kind() == ValueKind::FLOAT ? kSumF : kSumI, DataType(sum_type(c))};
     case WIN_ROLLING_MIN:
@@ -178,15 +196,16 @@ Checked check(const TablePtr &t, const std::vector<int> &part, const std::vector
         const WindowFunc rf = rolling_twin(s.func);
         CYLON_CHECK(t->Rows() < (int64_t(1) << 32), Code::Invalid,
                     "window " << fn << " over " << t->Rows() << " rows: framed functions take fewer than 2^32");
-        const bool sum = rf == WIN_ROLLING_SUM || rf == WIN_ROLLING_MEAN;
+        const bool sum = rf == WIN_ROLLING_SUM || rf == WIN_ROLLING_MEAN || is_moment(s.func);
         CYLON_CHECK(rf == WIN_ROLLING_COUNT || (scan_value(c) && !(sum && c.type.type == Type::HALF_FLOAT)),
                     Code::Invalid, "window " << fn << " needs a fixed-width numeric column, got " << c.type.ToString());
         CYLON_CHECK(s.preceding >= 0 && s.following >= 0, Code::Invalid,
                     "window " << fn << " frame of " << s.preceding << " preceding, " << s.following << " following");
         CYLON_CHECK(rf == WIN_ROLLING_COUNT || s.min_periods >= 1, Code::Invalid,
                     "window " << fn << " min_periods " << s.min_periods << " < 1");
+        CYLON_CHECK(!is_moment(s.func) || s.ddof >= 0, Code::Invalid, "window " << fn << " ddof " << s.ddof << " < 0");
       }
-      if (is_range(s.func)) {
+      if (is_range(s.func) || is_moment_range(s.func)) {
         CYLON_CHECK(order.size() == 1, Code::Invalid,
                     "window " << fn << " needs exactly one order column, got " << order.size());
         const Column &oc = t->column(order[0]);
@@ -220,7 +239,7 @@ Column int64_column(const std::string &name, const at::Tensor &v) {
 // navigation function's output is always nullable (NTH_VALUE past the partition's end), except the
 // fill of a column without nulls, which is the column itself; a distribution function's never is.
 bool nullable_result(const WindowSpec &s, const Column &c) {
-  if (is_pick(s.func)) return true;
+  if (is_pick(s.func) || is_moment(s.func)) return true;  // VAR / STD: null where m - ddof <= 0
   if (is_fill(s.func)) return c.nullable();
   if (s.func == WIN_CUMCOUNT || s.func == WIN_ROLLING_COUNT || s.func == WIN_RANGE_COUNT) return false;
   return c.nullable() || (is_framed(s.func) && s.min_periods > 1);
@@ -384,7 +403,8 @@ TablePtr Window(const TablePtr &t, const std::vector<int> &partition_cols, const
   bool rfloat = false;
   std::map<std::tuple<int, uint64_t, int, uint64_t>, Bounds> range_bounds;
   std::map<std::pair<int, int>, Pyramid> pyramids;  // by (value column, kernel function)
-  int64_t range_specs = 0;
+  std::map<int, Pyramid> moment_pyramids;           // by value column
+  int64_t range_specs = 0, moment_specs = 0;
   auto bounds_of = [&](const WindowSpec &s) -> const Bounds & {
     if (!rkeys.defined()) {
       const Column &oc = t->column(order_cols[0]);
@@ -430,6 +450,17 @@ TablePtr Window(const TablePtr &t, const std::vector<int> &partition_cols, const
     KCALL(ex, frame_range_pyramid, t->column(col).view(), n, func, u64(d.bits),
           d.valid.defined() ? ptr<uint8_t>(d.valid) : nullptr, u64(p.P), u64(p.S), u64(p.E));
     return pyramids.emplace(std::make_pair(col, func), p).first->second;
+  };
+
+  auto moment_pyramid_of = [&](int col) -> const Pyramid & {
+    auto it = moment_pyramids.find(col);
+    if (it != moment_pyramids.end()) return it->second;
+    const Dense &d = dense_of(col);
+    Pyramid p{ex.empty_i64(fm_words(fm_ps_slots(n))), ex.empty_i64(fm_words(fm_ps_slots(n))),
+              ex.empty_i64(fm_words(fm_e_slots(n)))};
+    KCALL(ex, frame_moments_pyramid, t->column(col).view(), n, u64(d.bits),
+          d.valid.defined() ? ptr<uint8_t>(d.valid) : nullptr, u64(p.P), u64(p.S), u64(p.E));
+    return moment_pyramids.emplace(col, p).first->second;
   };
 
   // fills: the tile pass and the carries once per (column, direction); pos = the fill position of
@@ -519,6 +550,22 @@ TablePtr Window(const TablePtr &t, const std::vector<int> &partition_cols, const
       KCALL(ex, window_shift, ptr<int64_t>(perm), ptr<int64_t>(phead), n, s.func == WIN_LAG ? -off : off,
             ptr<int64_t>(src));
       out.push_back(GatherColumn(c, src).with_name(name));
+      continue;
+    }
+    if (is_moment(s.func)) {
+      const Bounds *b = is_moment_range(s.func) ? &bounds_of(s) : nullptr;
+      const Dense &d = dense_of(s.col);
+      const Pyramid &mp = moment_pyramid_of(s.col);
+      Column col = make_fixed_column(name, DataType(Type::DOUBLE), n, ex.device, true);
+      KCALL(ex, frame_moments_apply, c.view(), ptr<int64_t>(perm), n,
+            s.func == WIN_ROLLING_STD || s.func == WIN_RANGE_STD, (int64_t)s.ddof, s.min_periods, u64(d.bits),
+            d.valid.defined() ? ptr<uint8_t>(d.valid) : nullptr, b != nullptr ? u32(b->lo) : nullptr,
+            b != nullptr ? u32(b->hi) : nullptr, ptr<int64_t>(phead), ptr<int64_t>(rtail), s.preceding, s.following,
+            u64(mp.P), u64(mp.S), u64(mp.E), reinterpret_cast<uint8_t *>(col.data.data_ptr()),
+            col.validity.data_ptr<uint8_t>());
+      ++moment_specs;
+      ++scans;
+      out.push_back(std::move(col));
       continue;
     }
     const auto plan = value_plan(s, c);
@@ -621,8 +668,13 @@ TablePtr Window(const TablePtr &t, const std::vector<int> &partition_cols, const
   if (frames_wide) trace::add_counter("window.frame.wide", frames_wide);
   if (range_specs) {
     trace::add_counter("window.frame.range", range_specs);
-    trace::add_counter("window.range.bounds", (int64_t)range_bounds.size());
     trace::add_counter("window.range.pyramids", (int64_t)pyramids.size());
+  }
+  // a RANGE VAR / STD spec searches (or shares) bounds too
+  if (!range_bounds.empty()) trace::add_counter("window.range.bounds", (int64_t)range_bounds.size());
+  if (moment_specs) {
+    trace::add_counter("window.frame.moment", moment_specs);
+    trace::add_counter("window.moment.pyramids", (int64_t)moment_pyramids.size());
   }
   return Table::Make(t->GetContext(), std::move(out));
 }

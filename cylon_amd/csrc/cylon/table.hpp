@@ -91,7 +91,8 @@ struct SortOptions {
 // RANGE BETWEEN preceding PRECEDING AND following FOLLOWING over the one order column.  The navigation
 // functions 19 .. 21 have the whole partition as their frame (not SQL's default frame), FFILL / BFILL
 // read back / ahead inside the partition, and the distribution functions 24 .. 26 need no column
-// (docs/semantics.md "Navigation and distribution functions").
+// (docs/semantics.md "Navigation and distribution functions").  Functions 27 .. 30 are VAR / STD over a
+// ROLLING resp. RANGE frame (docs/semantics.md "Framed aggregates", VAR / STD).
 enum WindowFunc : int {
   WIN_ROW_NUMBER = 0,
   WIN_RANK = 1,
@@ -120,6 +121,10 @@ enum WindowFunc : int {
   WIN_NTILE = 24,
   WIN_PERCENT_RANK = 25,
   WIN_CUME_DIST = 26,
+  WIN_ROLLING_VAR = 27,
+  WIN_ROLLING_STD = 28,
+  WIN_RANGE_VAR = 29,
+  WIN_RANGE_STD = 30,
 };
 
 constexpr int64_t kWindowUnbounded = INT64_MAX;  // a RANGE offset: no bound on that side
@@ -145,6 +150,9 @@ struct WindowSpec {
   bool ignore_nulls = false;
   // FFILL / BFILL: at most this many consecutive nulls after / before a value are filled (>= 0; 0: all)
   int64_t limit = 0;
+  // ROLLING / RANGE VAR and STD: the divisor is (non-null values of the frame) - ddof (>= 0); the result is
+  // null where that is not positive
+  int ddof = 1;
 };
 
 // As-of join (docs/semantics.md "As-of join"): every left row with the nearest right row of its group

@@ -380,6 +380,8 @@ class Table(PandasOpsMixin):
     # navigation and distribution functions: they go through C.window_nav
     _NAV_FUNCS = {"first_value": 19, "last_value": 20, "nth_value": 21, "ffill": 22, "bfill": 23, "ntile": 24,
                   "percent_rank": 25, "cume_dist": 26}
+    # VAR / STD over ROWS and RANGE frames: they go through C.window_moment_frames
+    _MOMENT_FUNCS = {"rolling_var": 27, "rolling_std": 28, "range_var": 29, "range_std": 30}
     _UNBOUNDED = (1 << 63) - 1
 
     @classmethod
@@ -396,6 +398,11 @@ class Table(PandasOpsMixin):
     def _is_nav(cls, spec):
         fn = spec if isinstance(spec, str) else (spec[0] if len(spec) > 0 else None)
         return isinstance(fn, str) and fn.lower() in cls._NAV_FUNCS
+
+    @classmethod
+    def _is_moment(cls, spec):
+        return (not isinstance(spec, str) and len(spec) > 0 and isinstance(spec[0], str)
+                and spec[0].lower() in cls._MOMENT_FUNCS)
 
     def _window_keys(self, partition_by, order_by, ascending):
         part = self._resolve_columns(partition_by) if partition_by is not None else []
@@ -473,6 +480,37 @@ class Table(PandasOpsMixin):
         if fid <= 20:
             return fid, self._resolve_column(spec[1]), 0, bool(opt), 0
         return fid, self._resolve_column(spec[1]), 0, False, 0 if opt is None else int(opt)
+
+    def _moment_spec(self, spec):
+        """(WindowFunc number, value column, preceding, following, preceding_f, following_f, offset_is_float,
+        min_periods, ddof) of a rolling_var / rolling_std / range_var / range_std spec; the frame is read as
+        rolling_mean resp. range_mean read theirs.  ddof < 0 and min_periods < 1 are the engine's to refuse"""
+        spec = tuple(spec)
+        fn = spec[0].lower()
+        if len(spec) < 4 or len(spec) > 6:
+            raise ValueError(f"window spec {spec!r}: expected ({fn!r}, column, preceding, following"
+                             f"[, min_periods[, ddof]])")
+        ddof = int(spec[5]) if len(spec) == 6 else 1
+        if fn.startswith("range_"):
+            _, col, p, f, pf, ff, isf, m = self._range_spec(("range_mean",) + spec[1:5])
+        else:
+            (_, col, p, f, m), (pf, ff, isf) = self._rolling_spec(("rolling_mean",) + spec[1:5]), (0.0, 0.0, False)
+        return self._MOMENT_FUNCS[fn], col, p, f, pf, ff, isf, m, ddof
+
+    def _window_moment_args(self, partition_by, order_by, ascending, funcs):
+        """_window_nav_args plus ddof, for a call with at least one moment (framed VAR / STD) spec"""
+        plain = {n: ("row_number" if self._is_moment(s) else s) for n, s in (funcs or {}).items()}
+        part, order, asc, *lists = self._window_nav_args(partition_by, order_by, ascending, plain)
+        ddof = []
+        for i, spec in enumerate((funcs or {}).values()):
+            d = 1
+            if self._is_moment(spec):
+                # ids, cols, args, names, pre, fol, pre_f, fol_f, is_float, minp, ignore_nulls, limit
+                fid, col, p, f, pf, ff, isf, m, d = self._moment_spec(spec)
+                for k, v in ((0, fid), (1, col), (4, p), (5, f), (6, pf), (7, ff), (8, isf), (9, m)):
+                    lists[k][i] = v
+            ddof.append(d)
+        return (part, order, asc, *lists, ddof)
 
     def _window_nav_args(self, partition_by, order_by, ascending, funcs):
         """_window_range_args plus ignore_nulls and limit, for a call with at least one navigation or
@@ -566,7 +604,20 @@ class Table(PandasOpsMixin):
         partition is cut into k runs whose sizes differ by at most one (the larger first),
         "percent_rank" = (rank - 1) / (rows - 1), 0.0 in a one-row partition, and "cume_dist" = the rows
         at or before the row's last peer / rows (docs/semantics.md "Navigation and distribution
-        functions")."""
+        functions").
+
+        Framed variance and standard deviation take the frames above: ("rolling_var" | "rolling_std",
+        column, preceding, following[, min_periods = 1[, ddof = 1]]) over the ROWS frame of rolling_mean,
+        ("range_var" | "range_std", ...) over the RANGE frame of range_mean, e.g. ("rolling_std", "v", 19,
+        0) for pandas rolling(20, min_periods=1).std() and ("rolling_std", "v", None, 0) for
+        expanding().std().  With m the frame's non-null values, each converted to float64, the float64
+        result is sum((x - mean)^2) / (m - ddof) or its square root: null where m < min_periods or
+        m - ddof <= 0, NaN where the frame holds a NaN or an infinity, never negative.  Every moment spec
+        of a column reads one pyramid of merged (count, mean, M2) states, so nothing cancels on data far
+        from zero (docs/semantics.md "Framed aggregates")."""
+        if any(self._is_moment(s) for s in (funcs or {}).values()):
+            return self._wrap(C.window_moment_frames(
+                self._t, *self._window_moment_args(partition_by, order_by, ascending, funcs)))
         if any(self._is_nav(s) for s in (funcs or {}).values()):
             return self._wrap(C.window_nav(self._t, *self._window_nav_args(partition_by, order_by, ascending, funcs)))
         if any(self._is_range(s) for s in (funcs or {}).values()):
@@ -580,8 +631,11 @@ class Table(PandasOpsMixin):
     def distributed_window(self, partition_by=None, order_by=None, ascending: Union[bool, List[bool]] = True,
                            funcs: dict = None) -> "Table":
         """window() after a shuffle by the partition columns (at least one when the world is larger than
-        1); the output row order is unspecified.  Rolling, range, navigation and distribution specs as in
-        window()."""
+        1); the output row order is unspecified.  Rolling, range, navigation, distribution and moment specs
+        as in window()."""
+        if any(self._is_moment(s) for s in (funcs or {}).values()):
+            return self._wrap(C.distributed_window_moment_frames(
+                self._t, *self._window_moment_args(partition_by, order_by, ascending, funcs)))
         if any(self._is_nav(s) for s in (funcs or {}).values()):
             return self._wrap(C.distributed_window_nav(
                 self._t, *self._window_nav_args(partition_by, order_by, ascending, funcs)))

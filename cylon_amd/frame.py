@@ -412,7 +412,9 @@ class DataFrame(object):
         rolling('5s', closed='both') on unique timestamps); a bound of None is unbounded.  Navigation and
         distribution functions: ("first_value" | "last_value", column[, ignore_nulls]) over the whole
         partition, ("nth_value", column, k), ("ffill" | "bfill", column[, limit]), ("ntile", k),
-        "percent_rank" and "cume_dist".  With an env
+        "percent_rank" and "cume_dist".  Framed variance and standard deviation: ("rolling_var" |
+        "rolling_std" | "range_var" | "range_std", column, preceding, following[, min_periods[, ddof = 1]]),
+        e.g. {"vol20": ("rolling_std", "ret", 19, 0)} for rolling(20, min_periods=1).std().  With an env
         of more than one rank the rows are first shuffled by the partition columns."""
         if env is None or env.world_size <= 1:
             return DataFrame(self._table.window(partition_by, order_by, ascending, funcs))

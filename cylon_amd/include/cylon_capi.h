@@ -96,6 +96,19 @@ int cylon_window_nav(const char *table_id, const int32_t *partition_columns, int
                      const int32_t *offset_is_float, const int64_t *min_periods, const int32_t *ignore_nulls,
                      const int64_t *limit, const char *const *names, int nspecs, int distributed,
                      const char *dest_id);
+/* cylon_window_nav with the framed VAR / STD too: also funcs[i] = 27 ROLLING_VAR, 28 ROLLING_STD (the frame
+   of ROLLING_MEAN), 29 RANGE_VAR, 30 RANGE_STD (the frame of RANGE_MEAN).  With m the non-null values of
+   the frame, each converted to float64, the result (float64) is sum (x - mean)^2 / (m - ddof[i]) or its
+   square root, null where m < min_periods[i] or m - ddof[i] <= 0, NaN where the frame holds a NaN or an
+   infinity; never negative.  ddof[i] >= 0; ddof may be NULL (1). */
+int cylon_window_moment_frames(const char *table_id, const int32_t *partition_columns, int npartition,
+                               const int32_t *order_columns, const int32_t *ascending, int norder,
+                               const int32_t *funcs, const int32_t *spec_columns, const int64_t *spec_args,
+                               const int64_t *preceding, const int64_t *following, const double *preceding_f,
+                               const double *following_f, const int32_t *offset_is_float,
+                               const int64_t *min_periods, const int32_t *ignore_nulls, const int64_t *limit,
+                               const int32_t *ddof, const char *const *names, int nspecs, int distributed,
+                               const char *dest_id);
 /* as-of join: every row of the left table, in its row order, with the columns of the nearest right row
    whose `by` columns equal its own (nby may be 0) -- direction 0 BACKWARD: the last right_on <=
    left_on, 1 FORWARD: the first right_on >= left_on, 2 NEAREST: the nearer of the two, the backward

@@ -66,7 +66,9 @@ def window(t: Table, partition_by=None, order_by=None, ascending: Union[bool, Li
     following[, min_periods]), or over a RANGE frame of the one order column's values, ("range_sum" | ... |
     "range_count", column, preceding, following[, min_periods]), and the navigation and distribution
     functions ("first_value" | "last_value", column[, ignore_nulls]), ("nth_value", column, k), ("ffill" |
-    "bfill", column[, limit]), ("ntile", k), "percent_rank", "cume_dist"."""
+    "bfill", column[, limit]), ("ntile", k), "percent_rank", "cume_dist", and the framed variance and
+    standard deviation ("rolling_var" | "rolling_std" | "range_var" | "range_std", column, preceding,
+    following[, min_periods[, ddof]])."""
     return t.window(partition_by, order_by, ascending, funcs)
 
 
