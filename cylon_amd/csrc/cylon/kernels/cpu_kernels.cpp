@@ -175,11 +175,12 @@ void gather_columns(const ColView *in, const MutColView *out, int ncols, const i
 }
 
 // K15 string <-> number casts (twins of strcast.hip; the parsers are shared in strparse.hpp)
-void str_to_i64(const ColView &c, int64_t n, int64_t *out, uint8_t *ok, void *) {
+void str_to_i64(const ColView &c, int64_t n, bool allow_neg, int64_t *out, uint8_t *ok, void *) {
   for (int64_t i = 0; i < n; ++i) {
     int64_t v = 0;
-    ok[i] = (!c.valid || c.valid[i]) ? strparse::sc_parse_i64(c.data + c.offsets[i], c.offsets[i + 1] - c.offsets[i], &v)
-                                     : 1;
+    ok[i] = (!c.valid || c.valid[i])
+                ? strparse::sc_parse_i64(c.data + c.offsets[i], c.offsets[i + 1] - c.offsets[i], allow_neg, &v)
+                : 1;
     out[i] = v;
   }
 }

@@ -28,8 +28,9 @@ void gather_columns(const ColView *in, const MutColView *out, int ncols, const i
    nullptr: always a), else b[b_bcast ? 0 : i]; b.offsets == nullptr selects a null row.  Output
    offsets = exclusive scan of the lengths; out_valid always written (may be nullptr) */
 /* strcast.hip: string -> int64 / float64 parse (ok[i]: 1 parsed, 0 invalid, 2 float needing the
-   host's correctly rounded parser), int64 -> decimal string (lengths, then digits at offsets) */
-void str_to_i64(const ColView &c, int64_t n, int64_t *out, uint8_t *ok, void *stream);
+   host's correctly rounded parser; allow_neg false: an unsigned target, a leading '-' is invalid),
+   int64 -> decimal string (lengths, then digits at offsets) */
+void str_to_i64(const ColView &c, int64_t n, bool allow_neg, int64_t *out, uint8_t *ok, void *stream);
 void str_to_f64(const ColView &c, int64_t n, double *out, uint8_t *ok, void *stream);
 void i64_to_str_lengths(const int64_t *v, const uint8_t *valid, int64_t n, int64_t *lens, void *stream);
 void i64_to_str_write(const int64_t *v, const uint8_t *valid, int64_t n, const int64_t *offs, uint8_t *bytes,

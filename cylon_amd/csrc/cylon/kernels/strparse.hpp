@@ -8,11 +8,13 @@
 namespace cylon {
 namespace strparse {
 
-CYLON_HD uint8_t sc_parse_i64(const uint8_t *s, int64_t len, int64_t *out) {
+// allow_neg: the target is signed; an unsigned target takes no '-' at all ("-0" does not parse)
+CYLON_HD uint8_t sc_parse_i64(const uint8_t *s, int64_t len, bool allow_neg, int64_t *out) {
   if (len <= 0) return 0;
   int64_t i = 0;
   bool neg = false;
   if (s[0] == '-') {  // Arrow's integer parser: '-' only, no '+'
+    if (!allow_neg) return 0;
     neg = true;
     i = 1;
     if (len == 1) return 0;

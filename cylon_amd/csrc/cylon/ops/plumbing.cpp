@@ -80,7 +80,7 @@ std::optional<Column> CastStringToNumber(const Column &c, const DataType &target
     KCALL(ex, str_to_f64, c.view(), n, ptr<double>(v), ptr<uint8_t>(ok));
   } else {
     v = ex.empty_i64(n);
-    KCALL(ex, str_to_i64, c.view(), n, ptr<int64_t>(v), ptr<uint8_t>(ok));
+    KCALL(ex, str_to_i64, c.view(), n, k == ValueKind::SIGNED_INT, ptr<int64_t>(v), ptr<uint8_t>(ok));
   }
   if (n) {
     at::Tensor okn = ok.slice(0, 0, n);
@@ -98,9 +98,17 @@ std::optional<Column> CastStringToNumber(const Column &c, const DataType &target
     CYLON_CHECK(mm[0] >= lo && mm[1] <= hi, Code::Invalid,
                 "cast: integer value out of range for " << target.ToString() << " in column " << c.name);
   }
-  if (!fl && k == ValueKind::UNSIGNED_INT && live.numel())
-    CYLON_CHECK(live.min().item<int64_t>() >= 0, Code::Invalid,
-                "cast: negative value for " << target.ToString() << " in column " << c.name);
+  // (an unsigned target has no negative value here: its parser takes no '-')
+  if (fl && target.width() == 4 && n) {
+    // binary64 -> binary32 rounds a second time.  That is the correctly rounded binary32 of the
+    // decimal unless the binary64 is exactly a binary32 midpoint (low 29 mantissa bits
+    // 0x10000000): the decimal may lie just beside it, and ties-to-even then goes the wrong way.
+    // Such a column goes to the host parser, which rounds to binary32 once.  Fast-path values are
+    // 0 or within 1e-22 .. 9.1e37, inside binary32's normal range, so no subnormal (other
+    // midpoints) and no overflow arise here; a null row holds 0.0, which is no midpoint.
+    at::Tensor low = at::bitwise_and(v.view(at::kLong), int64_t(0x1fffffff));
+    if ((low == int64_t(0x10000000)).any().item<bool>()) return std::nullopt;
+  }
   at::Tensor out = v.to(storage_dtype(target)).contiguous();
   return Column(c.name, target, n, out, at::Tensor(), c.validity);
 }

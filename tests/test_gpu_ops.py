@@ -413,4 +413,6 @@ def test_string_number_casts_on_device(gpu_ctx):
     out = t.astype({"i": pa.int64(), "f": pa.float64(), "x": pa.string()}).to_arrow()
     assert out.column("i").to_pylist() == pc.cast(s_int, pa.int64()).to_pylist()
     assert out.column("f").to_pylist() == pc.cast(s_flt, pa.float64()).to_pylist()
+    bits = lambda a: pc.fill_null(a, 0.0).to_numpy().view(np.uint64)  # noqa: E731  (-0.0 is not 0.0)
+    assert np.array_equal(bits(out.column("f").combine_chunks()), bits(pc.cast(s_flt, pa.float64())))
     assert out.column("x").to_pylist() == pc.cast(pa.array(ints, mask=mask), pa.string()).to_pylist()
