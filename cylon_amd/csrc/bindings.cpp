@@ -8,6 +8,7 @@
 
 #include "cylon/net/async_delay_communicator.hpp"
 #include "cylon/ctx/cylon_context.hpp"
+#include "cylon/kernels/strmatch_common.hpp"
 #include "cylon/net/channel.hpp"
 #include "cylon/net/communicator.hpp"
 #include "cylon/ops/api_ext.hpp"
@@ -330,6 +331,20 @@ PYBIND11_MODULE(_C, m) {
   m.def("select_var", &ops::SelectVar, py::arg("a"), py::arg("b"), py::arg("cond"), rel);
   m.def("cast_string_to_number", &ops::CastStringToNumber, py::arg("col"), py::arg("target"), rel);
   m.def("cast_integer_to_string", &ops::CastIntegerToString, py::arg("col"), py::arg("target"), rel);
+  // K15 string predicates (ops/strings.cpp); op / kind / unit: the numbers of strmatch_common.hpp
+  m.def("string_compare", &ops::StringCompare, py::arg("a"), py::arg("b"), py::arg("op"), rel);
+  m.def(
+      "string_match",
+      [](const Column &a, int kind, const py::bytes &pattern, const py::bytes &escape) {
+        const std::string p = pattern, e = escape;
+        CYLON_CHECK(e.size() == 1, Code::Invalid, "string_match: the escape must be one byte");
+        py::gil_scoped_release nogil;
+        return ops::StringMatch(a, kind, p, e[0]);
+      },
+      py::arg("a"), py::arg("kind"), py::arg("pattern"), py::arg("escape") = py::bytes("\\"));
+  m.def("string_length", &ops::StringLength, py::arg("a"), py::arg("unit"), rel);
+  m.def("string_tile_bytes", &ops::StringTileBytes, rel);
+  m.attr("string_max_pattern_bytes") = (int)strmatch::kStrMaxPatternBytes;
   m.def("project", &ops::Project, rel);
   m.def("merge", &ops::Merge, rel);
   m.def("slice", &ops::Slice, rel);

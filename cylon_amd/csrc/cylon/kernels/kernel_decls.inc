@@ -35,6 +35,17 @@ void str_to_f64(const ColView &c, int64_t n, double *out, uint8_t *ok, void *str
 void i64_to_str_lengths(const int64_t *v, const uint8_t *valid, int64_t n, int64_t *lens, void *stream);
 void i64_to_str_write(const int64_t *v, const uint8_t *valid, int64_t n, const int64_t *offs, uint8_t *bytes,
                       void *stream);
+/* strmatch.hip: K15 string predicates (docs/semantics.md "String predicates"); out[i] = 0 on a null
+   row, whose bytes are never read.  str_compare: a[i] op b[b_scalar ? 0 : i] (op: a StrCmpOp).
+   str_match: kind a StrMatchKind; pat (device memory) holds plen <= kStrMaxPatternBytes pattern
+   bytes, for STR_LIKE plen token kinds followed by plen token bytes; utf8 != 0: a match begins and
+   ends at code-point boundaries (LIKE over a STRING column).  str_length: unit a StrLenUnit.
+   string_tile_bytes: the largest byte span of 256 consecutive rows that takes the LDS-staged path */
+int64_t string_tile_bytes();
+void str_compare(const ColView &a, const ColView &b, int b_scalar, int op, int64_t n, uint8_t *out, void *stream);
+void str_match(const ColView &a, int kind, const uint8_t *pat, int64_t plen, int utf8, int64_t n, uint8_t *out,
+               void *stream);
+void str_length(const ColView &a, int unit, int64_t n, int64_t *out, void *stream);
 void select_var_lengths(const ColView &a, const ColView &b, int b_bcast, const uint8_t *cond, int64_t n,
                         int64_t *out_lens, void *stream);
 void select_var_bytes(const ColView &a, const ColView &b, int b_bcast, const uint8_t *cond, int64_t n,

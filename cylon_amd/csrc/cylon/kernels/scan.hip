@@ -344,6 +344,7 @@ void preload_select();
 void preload_semi_join();
 void preload_sort();
 void preload_strcast();
+void preload_strmatch();
 void preload_topk();
 void preload_window();
 void preload_window_nav();
@@ -377,6 +378,7 @@ void preload_device_code() {
   preload_semi_join();
   preload_sort();
   preload_strcast();
+  preload_strmatch();
   preload_topk();
   preload_window();
   preload_window_nav();

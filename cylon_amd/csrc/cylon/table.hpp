@@ -195,6 +195,20 @@ Column SelectVar(const Column &a, const std::optional<Column> &b, const at::Tens
 // (the caller then casts on the host); integer -> string.  Unparsable strings raise Invalid.
 std::optional<Column> CastStringToNumber(const Column &c, const DataType &target);
 Column CastIntegerToString(const Column &c, const DataType &target);
+// K15 string predicates on the column's device (kernels/strmatch.hip; docs/semantics.md "String
+// predicates").  a is a STRING or BINARY column; the result has a's length and name, is null where
+// an input cell is null and has a validity array iff an input column has one.
+//   StringCompare: BOOL a[i] op b[i], op a strmatch::StrCmpOp (== != < <= > >=); b has a's kind and
+//     a's length, or one row (broadcast).
+//   StringMatch: BOOL, kind a strmatch::StrMatchKind (STARTS_WITH, ENDS_WITH, CONTAINS with a literal
+//     byte pattern; LIKE with % _ and the escape character, a unit being a code point of a STRING
+//     column and a byte of a BINARY one).  A pattern of more than kStrMaxPatternBytes bytes, or a
+//     LIKE pattern that ends in a lone escape, is Invalid.
+//   StringLength: INT64, unit a strmatch::StrLenUnit (bytes; code points, STRING only).
+Column StringCompare(const Column &a, const Column &b, int op);
+Column StringMatch(const Column &a, int kind, const std::string &pattern, char escape);
+Column StringLength(const Column &a, int unit);
+int64_t StringTileBytes();  // kernels' string_tile_bytes(): the staged path's largest 256-row span
 TablePtr Project(const TablePtr &t, const std::vector<int> &cols);
 TablePtr Merge(const std::vector<TablePtr> &tables);  // vertical concat
 TablePtr Slice(const TablePtr &t, int64_t offset, int64_t length);

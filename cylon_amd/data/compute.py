@@ -3,8 +3,14 @@
 The reference evaluates these operators in Python/Cython over pyarrow.compute or
 numpy on the host.  Here fixed-width columns stay on the table's device and the
 operators run as device tensor expressions (ROCm kernels on MI355X), with the
-validity byte-mask propagated explicitly.  Variable-width (string) columns are
-evaluated by Arrow compute on the host, as in the reference.
+validity byte-mask propagated explicitly.  String / binary columns stay on the
+device too: where / fill_null (kernels/select.hip), the string <-> number casts
+(kernels/strcast.hip) and the string predicates (kernels/strmatch.hip) --
+comparisons of a string column with a str / bytes scalar or with a string column
+of the same kind, str_starts_with / str_ends_with / str_contains / str_like and
+str_length.  What does not fit those kernels (operands of different kinds, a
+pattern over C.string_max_pattern_bytes, arithmetic on strings) is evaluated by
+Arrow compute on the host, as in the reference, with the same values.
 
 Engine selection keeps the reference's `compute_engine` config key: "arrow"
 forces the host Arrow path, anything else uses the device path.
@@ -86,6 +92,11 @@ def binary_op(table, other, op: Callable, engine: str = "device"):
     out = []
     for i, c in enumerate(cols):
         oc = other_cols[i] if other_cols is not None else None
+        if engine != "arrow":
+            res = _string_compare(c, oc, other, op, dev)
+            if res is not None:
+                out.append(res)
+                continue
         use_arrow = engine == "arrow" or is_var(c) or (oc is not None and is_var(oc)) or isinstance(other, str)
         if use_arrow:
             fn = _CMP.get(op) or _ARITH.get(op) or {operator.and_: "and_kleene", operator.or_: "or_kleene"}.get(op)
@@ -158,6 +169,169 @@ def _select_var(c, other, cond, device):
         if b is None:
             return None
     return C.select_var(c, b, cond.to(torch.uint8))
+
+
+def is_text(col) -> bool:
+    return col.type.type in (T.STRING, T.BINARY)
+
+
+# the numbers of kernels/strmatch_common.hpp (StrCmpOp, StrMatchKind, StrLenUnit)
+_STR_CMP = {operator.eq: 0, operator.ne: 1, operator.lt: 2, operator.le: 3, operator.gt: 4, operator.ge: 5}
+_STR_KIND = {"starts_with": 0, "ends_with": 1, "contains": 2, "like": 3}
+_STR_UNIT = {"bytes": 0, "chars": 1}
+
+
+def _string_compare(c, oc, other, op, device):
+    """K15 device comparison of a string / binary column (kernels/strmatch.hip) with the column oc
+    of the same kind and length, or with the str / bytes scalar `other`; None when the operands do
+    not fit (the caller then uses Arrow's host kernels)."""
+    code = _STR_CMP.get(op)
+    if code is None or not is_text(c):
+        return None
+    if oc is not None:
+        if not is_text(oc) or oc.type.type != c.type.type or oc.length != c.length or \
+                oc.data.device != c.data.device:
+            return None
+        b = oc
+    elif isinstance(other, (str, bytes)):
+        b = _var_scalar(c, other, device)
+        if b is None:
+            return None
+    else:
+        return None
+    return C.string_compare(c, b, code)
+
+
+def _pattern_bytes(pattern) -> bytes:
+    if isinstance(pattern, str):
+        return pattern.encode("utf-8")
+    if isinstance(pattern, (bytes, bytearray)):
+        return bytes(pattern)
+    raise TypeError(f"a string pattern must be str or bytes, not {type(pattern).__name__}")
+
+
+def _engine_of(table, engine):
+    return engine or table.context.get_config("compute_engine", "device") or "device"
+
+
+def _text_columns(table, what):
+    cols = table.native.columns()
+    for c in cols:
+        if not is_text(c):
+            raise TypeError(f"{what}: column {c.name} ({c.type}) is not a string / binary column")
+    return cols
+
+
+def _arrow_like_pattern(pattern: bytes, escape: bytes) -> bytes:
+    """The LIKE pattern (bytes) rewritten for Arrow's match_like, whose escape character is the
+    backslash: an escaped %, _ or backslash stays escaped, any other escaped byte is literal."""
+    out, i = [], 0
+    while i < len(pattern):
+        ch = pattern[i:i + 1]
+        if ch == escape:
+            i += 1
+            if i >= len(pattern):
+                raise C.CylonError("like: the pattern ends in a lone escape character")
+            ch = pattern[i:i + 1]
+            out.append(b"\\" + ch if ch in (b"%", b"_", b"\\") else ch)
+        else:
+            out.append(b"\\\\" if ch == b"\\" else ch)
+        i += 1
+    return b"".join(out)
+
+
+def _str_match(table, kind, pattern, engine=None, escape="\\"):
+    cols = _text_columns(table, "str_" + kind)
+    pat = _pattern_bytes(pattern)
+    esc = _pattern_bytes(escape)
+    if len(esc) != 1:
+        raise ValueError("the escape must be one single-byte character")
+    out = []
+    if _engine_of(table, engine) == "arrow" or len(pat) > C.string_max_pattern_bytes:
+        for c in cols:
+            arr = _arrow_col(c)
+            if kind == "like":
+                res = pc.match_like(arr, _arrow_like_pattern(pat, esc))
+            else:
+                fn = {"starts_with": pc.starts_with, "ends_with": pc.ends_with, "contains": pc.match_substring}[kind]
+                res = fn(arr, pat)
+            out.append(_from_arrow(c.name, res, table.device))
+    else:
+        out = [C.string_match(c, _STR_KIND[kind], pat, esc) for c in cols]
+    return table._wrap(C.Table(table.native.context(), out))
+
+
+def str_starts_with(table, pattern, engine=None):
+    """BOOL per cell: the cell begins with the literal pattern (Arrow's starts_with); null for a
+    null cell.  Every column of the table must be string / binary."""
+    return _str_match(table, "starts_with", pattern, engine)
+
+
+def str_ends_with(table, pattern, engine=None):
+    """BOOL per cell: the cell ends with the literal pattern (Arrow's ends_with)."""
+    return _str_match(table, "ends_with", pattern, engine)
+
+
+def str_contains(table, pattern, engine=None):
+    """BOOL per cell: the literal pattern occurs in the cell (Arrow's match_substring; no regular
+    expressions)."""
+    return _str_match(table, "contains", pattern, engine)
+
+
+def str_like(table, pattern, escape="\\", engine=None):
+    """BOOL per cell: SQL LIKE anchored at both ends (Arrow's match_like): % any run, _ one code
+    point (one byte of a binary column), the escape makes the next character literal."""
+    return _str_match(table, "like", pattern, engine, escape)
+
+
+def str_length(table, unit="chars", engine=None):
+    """INT64 per cell: its length in code points (unit "chars", string columns only; Arrow's
+    utf8_length) or in bytes (unit "bytes"; Arrow's binary_length)."""
+    if unit not in _STR_UNIT:
+        raise ValueError(f"unit must be 'chars' or 'bytes', not {unit!r}")
+    cols = _text_columns(table, "str_length")
+    for c in cols:
+        if unit == "chars" and c.type.type != T.STRING:
+            raise TypeError(f"str_length: the binary column {c.name} has no code points")
+    if _engine_of(table, engine) == "arrow":
+        fn = pc.utf8_length if unit == "chars" else pc.binary_length
+        out = [_from_arrow(c.name, pc.cast(fn(_arrow_col(c)), pa.int64()), table.device) for c in cols]
+    else:
+        out = [C.string_length(c, _STR_UNIT[unit]) for c in cols]
+    return table._wrap(C.Table(table.native.context(), out))
+
+
+class StringMethods:
+    """The `.str` accessor of a Table / DataFrame whose columns are all string / binary: each method
+    returns a table of the same shape (BOOL or INT64 columns), so `t[t["name"].str.like("A%")]`
+    filters through __getitem__, where a null counts as false."""
+
+    def __init__(self, table, wrap=None):
+        self._table = table
+        self._wrap = wrap or (lambda t: t)
+
+    def startswith(self, pat):
+        return self._wrap(str_starts_with(self._table, pat))
+
+    def endswith(self, pat):
+        return self._wrap(str_ends_with(self._table, pat))
+
+    def contains(self, pat, regex=False):
+        """Literal substring test.  pandas' default is regex=True; here the default is the literal
+        match, and regex=True raises NotImplementedError (regular expressions are not supported)."""
+        if regex:
+            raise NotImplementedError("str.contains(regex=True): regular expressions are not supported")
+        return self._wrap(str_contains(self._table, pat))
+
+    def like(self, pattern, escape="\\"):
+        return self._wrap(str_like(self._table, pattern, escape))
+
+    def len(self):
+        """Length in code points."""
+        return self._wrap(str_length(self._table, "chars"))
+
+    def len_bytes(self):
+        return self._wrap(str_length(self._table, "bytes"))
 
 
 def fill_null(table, value):

@@ -304,3 +304,8 @@ class PandasOpsMixin:
             a = a.sort_by([(n, "ascending") for n in a.column_names])
             b = b.sort_by([(n, "ascending") for n in b.column_names])
         return a.equals(b)
+
+
+# t["name"].str.startswith(p) / .endswith / .contains / .like / .len / .len_bytes (compute.StringMethods);
+# attached here so that the name `str` inside the class body stays the builtin
+PandasOpsMixin.str = property(lambda self: compute.StringMethods(self), doc=compute.StringMethods.__doc__)

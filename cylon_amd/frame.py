@@ -476,6 +476,16 @@ class DataFrame(object):
         return DataFrame(self._change_context(env)._table.shuffle(on))
 
 
+def _frame_str(self):
+    from .data.compute import StringMethods
+    return StringMethods(self._table, DataFrame)
+
+
+# df["name"].str.*: the Table accessor with DataFrame results (attached here so that the name `str`
+# inside the class body stays the builtin)
+DataFrame.str = property(_frame_str, doc="String predicates of the columns (data/compute.py StringMethods).")
+
+
 class _FrameIndexer:
     def __init__(self, indexer):
         self._ix = indexer
