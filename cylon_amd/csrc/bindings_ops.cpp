@@ -47,6 +47,77 @@ static std::vector<ops::AggSpec> make_specs(const std::vector<int> &cols, const 
   return specs;
 }
 
+// Window specs as flat lists, one entry per spec.  max_func is the largest WindowFunc the entry point
+// accepts; it also says which lists the entry point has (each must be as long as funcs).  A list it does
+// not have arrives empty and leaves WindowSpec's default in every spec.
+using I64List = std::vector<int64_t>;
+static std::vector<WindowSpec> window_specs(int max_func, const std::vector<int> &funcs, const std::vector<int> &cols,
+                                            const I64List &args, const std::vector<std::string> &names,
+                                            const I64List &preceding = {}, const I64List &following = {},
+                                            const std::vector<double> &preceding_f = {},
+                                            const std::vector<double> &following_f = {},
+                                            const std::vector<bool> &offset_is_float = {},
+                                            const I64List &min_periods = {}, const std::vector<bool> &ignore_nulls = {},
+                                            const I64List &limit = {}, const std::vector<int> &ddof = {}) {
+  const size_t k = funcs.size();
+  auto fits = [&](size_t size, int since) { return size == (max_func >= since ? k : 0); };
+  CYLON_CHECK(cols.size() == k && args.size() == k && names.size() == k && fits(preceding.size(), WIN_ROLLING_COUNT) &&
+                  fits(following.size(), WIN_ROLLING_COUNT) && fits(min_periods.size(), WIN_ROLLING_COUNT) &&
+                  fits(preceding_f.size(), WIN_RANGE_COUNT) && fits(following_f.size(), WIN_RANGE_COUNT) &&
+                  fits(offset_is_float.size(), WIN_RANGE_COUNT) && fits(ignore_nulls.size(), WIN_FIRST_VALUE) &&
+                  fits(limit.size(), WIN_FIRST_VALUE) && fits(ddof.size(), WIN_ROLLING_VAR),
+              Code::Invalid, "window spec lists differ in length");
+  std::vector<WindowSpec> specs(k);
+  for (size_t i = 0; i < k; ++i) {
+    CYLON_CHECK(funcs[i] >= WIN_ROW_NUMBER && funcs[i] <= max_func, Code::Invalid, "window function " << funcs[i]);
+    WindowSpec &s = specs[i];
+    s.func = static_cast<WindowFunc>(funcs[i]);
+    s.col = cols[i];
+    s.arg = args[i];
+    s.name = names[i];
+    if (!preceding.empty()) s.preceding = preceding[i];
+    if (!following.empty()) s.following = following[i];
+    if (!min_periods.empty()) s.min_periods = min_periods[i];
+    if (!preceding_f.empty()) s.preceding_f = preceding_f[i];
+    if (!following_f.empty()) s.following_f = following_f[i];
+    if (!offset_is_float.empty()) s.offset_is_float = offset_is_float[i];
+    if (!ignore_nulls.empty()) s.ignore_nulls = ignore_nulls[i];
+    if (!limit.empty()) s.limit = limit[i];
+    if (!ddof.empty()) s.ddof = ddof[i];
+  }
+  return specs;
+}
+
+// C.window_frames' list order: min_periods follows the ROWS frame
+static std::vector<WindowSpec> window_specs(int max_func, const std::vector<int> &funcs, const std::vector<int> &cols,
+                                            const I64List &args, const std::vector<std::string> &names,
+                                            const I64List &preceding, const I64List &following,
+                                            const I64List &min_periods) {
+  return window_specs(max_func, funcs, cols, args, names, preceding, following, {}, {}, {}, min_periods);
+}
+
+// NAME(table, partition_cols, order_cols, ascending, lists..., carry_step_tiles = 0) and distributed_NAME
+// without the carry step; Lists = the types of the spec lists, list_args their Python names
+template <typename... Lists, typename... Args>
+static void def_window(py::module &m, const std::string &name, int max_func, const Args &...list_args) {
+  const auto rel = py::call_guard<py::gil_scoped_release>();
+  m.def(
+      name.c_str(),
+      [max_func](const TablePtr &t, const std::vector<int> &part, const std::vector<int> &order,
+                 const std::vector<bool> &asc, const Lists &...lists, int64_t carry_step_tiles) {
+        return ops::Window(t, part, order, asc, window_specs(max_func, lists...), carry_step_tiles);
+      },
+      py::arg("table"), py::arg("partition_cols"), py::arg("order_cols"), py::arg("ascending"), list_args...,
+      py::arg("carry_step_tiles") = 0, rel);
+  m.def(
+      ("distributed_" + name).c_str(),
+      [max_func](const TablePtr &t, const std::vector<int> &part, const std::vector<int> &order,
+                 const std::vector<bool> &asc, const Lists &...lists) {
+        return ops::DistributedWindow(t, part, order, asc, window_specs(max_func, lists...));
+      },
+      py::arg("table"), py::arg("partition_cols"), py::arg("order_cols"), py::arg("ascending"), list_args..., rel);
+}
+
 void register_extended_ops(py::module &m) {
   auto rel = py::call_guard<py::gil_scoped_release>();
 
@@ -295,258 +366,36 @@ void register_extended_ops(py::module &m) {
   m.def("topk", &ops::TopK, py::arg("table"), py::arg("cols"), py::arg("ascending"), py::arg("k"), rel);
   m.def("distributed_topk", &ops::DistributedTopK, py::arg("table"), py::arg("cols"), py::arg("ascending"),
         py::arg("k"), rel);
-  // window functions: specs as flat lists (WindowFunc numbers, value columns, LAG / LEAD offsets, output names)
-  auto window_specs = [](const std::vector<int> &funcs, const std::vector<int> &cols, const std::vector<int64_t> &args,
-                         const std::vector<std::string> &names) {
-    CYLON_CHECK(funcs.size() == cols.size() && funcs.size() == args.size() && funcs.size() == names.size(),
-                Code::Invalid, "window spec lists differ in length");
-    std::vector<WindowSpec> specs;
-    for (size_t i = 0; i < funcs.size(); ++i) {
-      CYLON_CHECK(funcs[i] >= WIN_ROW_NUMBER && funcs[i] <= WIN_LEAD, Code::Invalid, "window function " << funcs[i]);
-      specs.push_back({static_cast<WindowFunc>(funcs[i]), cols[i], args[i], names[i]});
-    }
-    return specs;
-  };
-  m.def(
-      "window",
-      [window_specs](const TablePtr &t, const std::vector<int> &part, const std::vector<int> &order,
-                     const std::vector<bool> &asc, const std::vector<int> &funcs, const std::vector<int> &cols,
-                     const std::vector<int64_t> &args, const std::vector<std::string> &names, int64_t carry_step_tiles) {
-        return ops::Window(t, part, order, asc, window_specs(funcs, cols, args, names), carry_step_tiles);
-      },
-      py::arg("table"), py::arg("partition_cols"), py::arg("order_cols"), py::arg("ascending"), py::arg("funcs"),
-      py::arg("cols"), py::arg("args"), py::arg("names"), py::arg("carry_step_tiles") = 0, rel);
-  m.def(
-      "distributed_window",
-      [window_specs](const TablePtr &t, const std::vector<int> &part, const std::vector<int> &order,
-                     const std::vector<bool> &asc, const std::vector<int> &funcs, const std::vector<int> &cols,
-                     const std::vector<int64_t> &args, const std::vector<std::string> &names) {
-        return ops::DistributedWindow(t, part, order, asc, window_specs(funcs, cols, args, names));
-      },
-      py::arg("table"), py::arg("partition_cols"), py::arg("order_cols"), py::arg("ascending"), py::arg("funcs"),
-      py::arg("cols"), py::arg("args"), py::arg("names"), rel);
-  // the same with a frame per spec (ROLLING functions: rows before and after the current one, >= the
-  // table's rows meaning unbounded, and min_periods); accepts every WindowFunc
-  auto frame_specs = [](const std::vector<int> &funcs, const std::vector<int> &cols, const std::vector<int64_t> &args,
-                        const std::vector<std::string> &names, const std::vector<int64_t> &preceding,
-                        const std::vector<int64_t> &following, const std::vector<int64_t> &min_periods) {
-    const size_t k = funcs.size();
-    CYLON_CHECK(cols.size() == k && args.size() == k && names.size() == k && preceding.size() == k &&
-                    following.size() == k && min_periods.size() == k,
-                Code::Invalid, "window spec lists differ in length");
-    std::vector<WindowSpec> specs;
-    for (size_t i = 0; i < k; ++i) {
-      CYLON_CHECK(funcs[i] >= WIN_ROW_NUMBER && funcs[i] <= WIN_ROLLING_MAX, Code::Invalid,
-                  "window function " << funcs[i]);
-      specs.push_back({static_cast<WindowFunc>(funcs[i]), cols[i], args[i], names[i], preceding[i], following[i],
-                       min_periods[i]});
-    }
-    return specs;
-  };
-  m.def(
-      "window_frames",
-      [frame_specs](const TablePtr &t, const std::vector<int> &part, const std::vector<int> &order,
-                    const std::vector<bool> &asc, const std::vector<int> &funcs, const std::vector<int> &cols,
-                    const std::vector<int64_t> &args, const std::vector<std::string> &names,
-                    const std::vector<int64_t> &preceding, const std::vector<int64_t> &following,
-                    const std::vector<int64_t> &min_periods, int64_t carry_step_tiles) {
-        return ops::Window(t, part, order, asc, frame_specs(funcs, cols, args, names, preceding, following, min_periods),
-                           carry_step_tiles);
-      },
-      py::arg("table"), py::arg("partition_cols"), py::arg("order_cols"), py::arg("ascending"), py::arg("funcs"),
-      py::arg("cols"), py::arg("args"), py::arg("names"), py::arg("preceding"), py::arg("following"),
-      py::arg("min_periods"), py::arg("carry_step_tiles") = 0, rel);
-  m.def(
-      "distributed_window_frames",
-      [frame_specs](const TablePtr &t, const std::vector<int> &part, const std::vector<int> &order,
-                    const std::vector<bool> &asc, const std::vector<int> &funcs, const std::vector<int> &cols,
-                    const std::vector<int64_t> &args, const std::vector<std::string> &names,
-                    const std::vector<int64_t> &preceding, const std::vector<int64_t> &following,
-                    const std::vector<int64_t> &min_periods) {
-        return ops::DistributedWindow(t, part, order, asc,
-                                      frame_specs(funcs, cols, args, names, preceding, following, min_periods));
-      },
-      py::arg("table"), py::arg("partition_cols"), py::arg("order_cols"), py::arg("ascending"), py::arg("funcs"),
-      py::arg("cols"), py::arg("args"), py::arg("names"), py::arg("preceding"), py::arg("following"),
-      py::arg("min_periods"), rel);
-  // the same with RANGE frames too (functions 0 .. 18): preceding / following are then distances in the
-  // order column's values, INT64_MAX meaning unbounded; where offset_is_float[i], a side that is not
-  // unbounded reads preceding_f[i] / following_f[i] instead
-  auto range_specs = [](const std::vector<int> &funcs, const std::vector<int> &cols, const std::vector<int64_t> &args,
-                        const std::vector<std::string> &names, const std::vector<int64_t> &preceding,
-                        const std::vector<int64_t> &following, const std::vector<double> &preceding_f,
-                        const std::vector<double> &following_f, const std::vector<bool> &offset_is_float,
-                        const std::vector<int64_t> &min_periods) {
-    const size_t k = funcs.size();
-    CYLON_CHECK(cols.size() == k && args.size() == k && names.size() == k && preceding.size() == k &&
-                    following.size() == k && preceding_f.size() == k && following_f.size() == k &&
-                    offset_is_float.size() == k && min_periods.size() == k,
-                Code::Invalid, "window spec lists differ in length");
-    std::vector<WindowSpec> specs;
-    for (size_t i = 0; i < k; ++i) {
-      CYLON_CHECK(funcs[i] >= WIN_ROW_NUMBER && funcs[i] <= WIN_RANGE_MAX, Code::Invalid,
-                  "window function " << funcs[i]);
-      specs.push_back({static_cast<WindowFunc>(funcs[i]), cols[i], args[i], names[i], preceding[i], following[i],
-                       min_periods[i], preceding_f[i], following_f[i], offset_is_float[i]});
-    }
-    return specs;
-  };
-  m.def(
-      "window_range_frames",
-      [range_specs](const TablePtr &t, const std::vector<int> &part, const std::vector<int> &order,
-                    const std::vector<bool> &asc, const std::vector<int> &funcs, const std::vector<int> &cols,
-                    const std::vector<int64_t> &args, const std::vector<std::string> &names,
-                    const std::vector<int64_t> &preceding, const std::vector<int64_t> &following,
-                    const std::vector<double> &preceding_f, const std::vector<double> &following_f,
-                    const std::vector<bool> &offset_is_float, const std::vector<int64_t> &min_periods,
-                    int64_t carry_step_tiles) {
-        return ops::Window(t, part, order, asc,
-                           range_specs(funcs, cols, args, names, preceding, following, preceding_f, following_f,
-                                       offset_is_float, min_periods),
-                           carry_step_tiles);
-      },
-      py::arg("table"), py::arg("partition_cols"), py::arg("order_cols"), py::arg("ascending"), py::arg("funcs"),
-      py::arg("cols"), py::arg("args"), py::arg("names"), py::arg("preceding"), py::arg("following"),
-      py::arg("preceding_f"), py::arg("following_f"), py::arg("offset_is_float"), py::arg("min_periods"),
-      py::arg("carry_step_tiles") = 0, rel);
-  m.def(
-      "distributed_window_range_frames",
-      [range_specs](const TablePtr &t, const std::vector<int> &part, const std::vector<int> &order,
-                    const std::vector<bool> &asc, const std::vector<int> &funcs, const std::vector<int> &cols,
-                    const std::vector<int64_t> &args, const std::vector<std::string> &names,
-                    const std::vector<int64_t> &preceding, const std::vector<int64_t> &following,
-                    const std::vector<double> &preceding_f, const std::vector<double> &following_f,
-                    const std::vector<bool> &offset_is_float, const std::vector<int64_t> &min_periods) {
-        return ops::DistributedWindow(t, part, order, asc,
-                                      range_specs(funcs, cols, args, names, preceding, following, preceding_f,
-                                                  following_f, offset_is_float, min_periods));
-      },
-      py::arg("table"), py::arg("partition_cols"), py::arg("order_cols"), py::arg("ascending"), py::arg("funcs"),
-      py::arg("cols"), py::arg("args"), py::arg("names"), py::arg("preceding"), py::arg("following"),
-      py::arg("preceding_f"), py::arg("following_f"), py::arg("offset_is_float"), py::arg("min_periods"), rel);
-  // the same with the navigation and distribution functions too (functions 0 .. 26): ignore_nulls[i] for
-  // FIRST_VALUE / LAST_VALUE, limit[i] (0: none) for FFILL / BFILL; NTH_VALUE and NTILE read k from args[i]
-  auto nav_specs = [range_specs](const std::vector<int> &funcs, const std::vector<int> &cols,
-                                 const std::vector<int64_t> &args, const std::vector<std::string> &names,
-                                 const std::vector<int64_t> &preceding, const std::vector<int64_t> &following,
-                                 const std::vector<double> &preceding_f, const std::vector<double> &following_f,
-                                 const std::vector<bool> &offset_is_float, const std::vector<int64_t> &min_periods,
-                                 const std::vector<bool> &ignore_nulls, const std::vector<int64_t> &limit) {
-    const size_t k = funcs.size();
-    CYLON_CHECK(ignore_nulls.size() == k && limit.size() == k, Code::Invalid, "window spec lists differ in length");
-    std::vector<int> known = funcs;  // range_specs checks the other lists and knows functions 0 .. 18
-    for (size_t i = 0; i < k; ++i) {
-      CYLON_CHECK(funcs[i] >= WIN_ROW_NUMBER && funcs[i] <= WIN_CUME_DIST, Code::Invalid,
-                  "window function " << funcs[i]);
-      if (funcs[i] > WIN_RANGE_MAX) known[i] = WIN_ROW_NUMBER;
-    }
-    std::vector<WindowSpec> specs = range_specs(known, cols, args, names, preceding, following, preceding_f,
-                                                following_f, offset_is_float, min_periods);
-    for (size_t i = 0; i < k; ++i) {
-      specs[i].func = static_cast<WindowFunc>(funcs[i]);
-      specs[i].ignore_nulls = ignore_nulls[i];
-      specs[i].limit = limit[i];
-    }
-    return specs;
-  };
-  m.def(
-      "window_nav",
-      [nav_specs](const TablePtr &t, const std::vector<int> &part, const std::vector<int> &order,
-                  const std::vector<bool> &asc, const std::vector<int> &funcs, const std::vector<int> &cols,
-                  const std::vector<int64_t> &args, const std::vector<std::string> &names,
-                  const std::vector<int64_t> &preceding, const std::vector<int64_t> &following,
-                  const std::vector<double> &preceding_f, const std::vector<double> &following_f,
-                  const std::vector<bool> &offset_is_float, const std::vector<int64_t> &min_periods,
-                  const std::vector<bool> &ignore_nulls, const std::vector<int64_t> &limit, int64_t carry_step_tiles) {
-        return ops::Window(t, part, order, asc,
-                           nav_specs(funcs, cols, args, names, preceding, following, preceding_f, following_f,
-                                     offset_is_float, min_periods, ignore_nulls, limit),
-                           carry_step_tiles);
-      },
-      py::arg("table"), py::arg("partition_cols"), py::arg("order_cols"), py::arg("ascending"), py::arg("funcs"),
-      py::arg("cols"), py::arg("args"), py::arg("names"), py::arg("preceding"), py::arg("following"),
-      py::arg("preceding_f"), py::arg("following_f"), py::arg("offset_is_float"), py::arg("min_periods"),
-      py::arg("ignore_nulls"), py::arg("limit"), py::arg("carry_step_tiles") = 0, rel);
-  m.def(
-      "distributed_window_nav",
-      [nav_specs](const TablePtr &t, const std::vector<int> &part, const std::vector<int> &order,
-                  const std::vector<bool> &asc, const std::vector<int> &funcs, const std::vector<int> &cols,
-                  const std::vector<int64_t> &args, const std::vector<std::string> &names,
-                  const std::vector<int64_t> &preceding, const std::vector<int64_t> &following,
-                  const std::vector<double> &preceding_f, const std::vector<double> &following_f,
-                  const std::vector<bool> &offset_is_float, const std::vector<int64_t> &min_periods,
-                  const std::vector<bool> &ignore_nulls, const std::vector<int64_t> &limit) {
-        return ops::DistributedWindow(t, part, order, asc,
-                                      nav_specs(funcs, cols, args, names, preceding, following, preceding_f,
-                                                following_f, offset_is_float, min_periods, ignore_nulls, limit));
-      },
-      py::arg("table"), py::arg("partition_cols"), py::arg("order_cols"), py::arg("ascending"), py::arg("funcs"),
-      py::arg("cols"), py::arg("args"), py::arg("names"), py::arg("preceding"), py::arg("following"),
-      py::arg("preceding_f"), py::arg("following_f"), py::arg("offset_is_float"), py::arg("min_periods"),
-      py::arg("ignore_nulls"), py::arg("limit"), rel);
-  // the same with VAR / STD over ROWS and RANGE frames too (functions 0 .. 30): ddof[i] for functions
-  // 27 .. 30, which read their frame as ROLLING_MEAN resp. RANGE_MEAN do
-  auto moment_specs = [nav_specs](const std::vector<int> &funcs, const std::vector<int> &cols,
-                                  const std::vector<int64_t> &args, const std::vector<std::string> &names,
-                                  const std::vector<int64_t> &preceding, const std::vector<int64_t> &following,
-                                  const std::vector<double> &preceding_f, const std::vector<double> &following_f,
-                                  const std::vector<bool> &offset_is_float, const std::vector<int64_t> &min_periods,
-                                  const std::vector<bool> &ignore_nulls, const std::vector<int64_t> &limit,
-                                  const std::vector<int> &ddof) {
-    const size_t k = funcs.size();
-    CYLON_CHECK(ddof.size() == k, Code::Invalid, "window spec lists differ in length");
-    std::vector<int> known = funcs;  // nav_specs checks the other lists and knows functions 0 .. 26
-    for (size_t i = 0; i < k; ++i) {
-      CYLON_CHECK(funcs[i] >= WIN_ROW_NUMBER && funcs[i] <= WIN_RANGE_STD, Code::Invalid,
-                  "window function " << funcs[i]);
-      if (funcs[i] > WIN_CUME_DIST) known[i] = WIN_ROW_NUMBER;
-    }
-    std::vector<WindowSpec> specs = nav_specs(known, cols, args, names, preceding, following, preceding_f,
-                                              following_f, offset_is_float, min_periods, ignore_nulls, limit);
-    for (size_t i = 0; i < k; ++i) {
-      specs[i].func = static_cast<WindowFunc>(funcs[i]);
-      specs[i].ddof = ddof[i];
-    }
-    return specs;
-  };
-  m.def(
-      "window_moment_frames",
-      [moment_specs](const TablePtr &t, const std::vector<int> &part, const std::vector<int> &order,
-                     const std::vector<bool> &asc, const std::vector<int> &funcs, const std::vector<int> &cols,
-                     const std::vector<int64_t> &args, const std::vector<std::string> &names,
-                     const std::vector<int64_t> &preceding, const std::vector<int64_t> &following,
-                     const std::vector<double> &preceding_f, const std::vector<double> &following_f,
-                     const std::vector<bool> &offset_is_float, const std::vector<int64_t> &min_periods,
-                     const std::vector<bool> &ignore_nulls, const std::vector<int64_t> &limit,
-                     const std::vector<int> &ddof, int64_t carry_step_tiles) {
-        return ops::Window(t, part, order, asc,
-                           moment_specs(funcs, cols, args, names, preceding, following, preceding_f, following_f,
-                                        offset_is_float, min_periods, ignore_nulls, limit, ddof),
-                           carry_step_tiles);
-      },
-      py::arg("table"), py::arg("partition_cols"), py::arg("order_cols"), py::arg("ascending"), py::arg("funcs"),
-      py::arg("cols"), py::arg("args"), py::arg("names"), py::arg("preceding"), py::arg("following"),
-      py::arg("preceding_f"), py::arg("following_f"), py::arg("offset_is_float"), py::arg("min_periods"),
-      py::arg("ignore_nulls"), py::arg("limit"), py::arg("ddof"), py::arg("carry_step_tiles") = 0, rel);
-  m.def(
-      "distributed_window_moment_frames",
-      [moment_specs](const TablePtr &t, const std::vector<int> &part, const std::vector<int> &order,
-                     const std::vector<bool> &asc, const std::vector<int> &funcs, const std::vector<int> &cols,
-                     const std::vector<int64_t> &args, const std::vector<std::string> &names,
-                     const std::vector<int64_t> &preceding, const std::vector<int64_t> &following,
-                     const std::vector<double> &preceding_f, const std::vector<double> &following_f,
-                     const std::vector<bool> &offset_is_float, const std::vector<int64_t> &min_periods,
-                     const std::vector<bool> &ignore_nulls, const std::vector<int64_t> &limit,
-                     const std::vector<int> &ddof) {
-        return ops::DistributedWindow(t, part, order, asc,
-                                      moment_specs(funcs, cols, args, names, preceding, following, preceding_f,
-                                                   following_f, offset_is_float, min_periods, ignore_nulls, limit,
-                                                   ddof));
-      },
-      py::arg("table"), py::arg("partition_cols"), py::arg("order_cols"), py::arg("ascending"), py::arg("funcs"),
-      py::arg("cols"), py::arg("args"), py::arg("names"), py::arg("preceding"), py::arg("following"),
-      py::arg("preceding_f"), py::arg("following_f"), py::arg("offset_is_float"), py::arg("min_periods"),
-      py::arg("ignore_nulls"), py::arg("limit"), py::arg("ddof"), rel);
+  // Window functions, one entry point per level (window_specs above); each accepts the functions of the
+  // levels before it too.  args: LAG / LEAD offsets, and k of NTH_VALUE and NTILE.
+  using Ints = std::vector<int>;
+  using Names = std::vector<std::string>;
+  using Doubles = std::vector<double>;
+  using Bools = std::vector<bool>;
+  const py::arg funcs("funcs"), cols("cols"), args("args"), names("names"), preceding("preceding"),
+      following("following"), preceding_f("preceding_f"), following_f("following_f"),
+      offset_is_float("offset_is_float"), min_periods("min_periods"), ignore_nulls("ignore_nulls"), limit("limit"),
+      ddof("ddof");
+  def_window<Ints, Ints, I64List, Names>(m, "window", WIN_LEAD, funcs, cols, args, names);
+  // ROLLING functions: a ROWS frame per spec (rows before and after the current one, >= the table's rows
+  // meaning unbounded) and min_periods
+  def_window<Ints, Ints, I64List, Names, I64List, I64List, I64List>(m, "window_frames", WIN_ROLLING_MAX, funcs, cols,
+                                                                    args, names, preceding, following, min_periods);
+  // RANGE functions: preceding / following are then distances in the order column's values, INT64_MAX
+  // meaning unbounded; where offset_is_float[i], a side that is not unbounded reads preceding_f[i] /
+  // following_f[i] instead
+  def_window<Ints, Ints, I64List, Names, I64List, I64List, Doubles, Doubles, Bools, I64List>(
+      m, "window_range_frames", WIN_RANGE_MAX, funcs, cols, args, names, preceding, following, preceding_f, following_f,
+      offset_is_float, min_periods);
+  // navigation and distribution functions: ignore_nulls[i] for FIRST_VALUE / LAST_VALUE, limit[i] (0: none)
+  // for FFILL / BFILL
+  def_window<Ints, Ints, I64List, Names, I64List, I64List, Doubles, Doubles, Bools, I64List, Bools, I64List>(
+      m, "window_nav", WIN_CUME_DIST, funcs, cols, args, names, preceding, following, preceding_f, following_f,
+      offset_is_float, min_periods, ignore_nulls, limit);
+  // VAR / STD over ROWS and RANGE frames: ddof[i]; they read their frame as ROLLING_MEAN resp. RANGE_MEAN do
+  def_window<Ints, Ints, I64List, Names, I64List, I64List, Doubles, Doubles, Bools, I64List, Bools, I64List, Ints>(
+      m, "window_moment_frames", WIN_RANGE_STD, funcs, cols, args, names, preceding, following, preceding_f,
+      following_f, offset_is_float, min_periods, ignore_nulls, limit, ddof);
   // as-of join: tolerance = None, an int (integer / temporal `on`) or a float (float `on`)
   auto asof_options = [](int direction, bool allow_exact, const py::object &tolerance, const std::string &left_prefix,
                          const std::string &right_prefix) {

@@ -165,19 +165,38 @@ CYLON_CAPI int cylon_topk(const char *id, int column, int ascending, int64_t k, 
   return guard([&] { return status(TopKTable(id, column, k, dest, ascending != 0)); });
 }
 
-CYLON_CAPI int cylon_window(const char *id, const int32_t *partition_cols, int npartition, const int32_t *order_cols,
-                            const int32_t *ascending, int norder, const int32_t *funcs, const int32_t *spec_cols,
-                            const int64_t *spec_args, const char *const *names, int nspecs, int distributed,
-                            const char *dest) {
+// The window entry points: max_func is the largest WindowFunc the entry point accepts; a null list (one
+// the entry point does not have, or one the caller left out) leaves the default in every spec: column -1,
+// argument 0, name "", and WindowSpec's own for the rest (min_periods 1, ddof 1).
+static int window_call(const char *id, const int32_t *partition_cols, int npartition, const int32_t *order_cols,
+                       const int32_t *ascending, int norder, int nspecs, int distributed, const char *dest,
+                       int max_func, const int32_t *funcs, const int32_t *spec_cols, const int64_t *spec_args,
+                       const char *const *names, const int64_t *preceding = nullptr,
+                       const int64_t *following = nullptr, const int64_t *min_periods = nullptr,
+                       const double *preceding_f = nullptr, const double *following_f = nullptr,
+                       const int32_t *offset_is_float = nullptr, const int32_t *ignore_nulls = nullptr,
+                       const int64_t *limit = nullptr, const int32_t *ddof = nullptr) {
   return guard([&] {
     std::vector<bool> dirs;
     for (int i = 0; i < norder; ++i) dirs.push_back(ascending == nullptr || ascending[i] != 0);
-    std::vector<WindowSpec> specs;
+    std::vector<WindowSpec> specs(nspecs > 0 ? nspecs : 0);
     for (int i = 0; i < nspecs; ++i) {
-      if (funcs[i] < WIN_ROW_NUMBER || funcs[i] > WIN_LEAD)
+      if (funcs[i] < WIN_ROW_NUMBER || funcs[i] > max_func)
         return status(Status(Code::Invalid, "window function " + std::to_string(funcs[i])));
-      specs.push_back({static_cast<WindowFunc>(funcs[i]), spec_cols ? spec_cols[i] : -1, spec_args ? spec_args[i] : 0,
-                       names && names[i] ? names[i] : ""});
+      WindowSpec &s = specs[i];
+      s.func = static_cast<WindowFunc>(funcs[i]);
+      s.col = spec_cols ? spec_cols[i] : -1;
+      s.arg = spec_args ? spec_args[i] : 0;
+      if (names && names[i]) s.name = names[i];
+      if (preceding) s.preceding = preceding[i];
+      if (following) s.following = following[i];
+      if (min_periods) s.min_periods = min_periods[i];
+      if (preceding_f) s.preceding_f = preceding_f[i];
+      if (following_f) s.following_f = following_f[i];
+      if (offset_is_float) s.offset_is_float = offset_is_float[i] != 0;
+      if (ignore_nulls) s.ignore_nulls = ignore_nulls[i] != 0;
+      if (limit) s.limit = limit[i];
+      if (ddof) s.ddof = ddof[i];
     }
     return status(WindowTable(id, std::vector<int32_t>(partition_cols, partition_cols + npartition),
                               std::vector<int32_t>(order_cols, order_cols + norder), dirs, specs, dest,
@@ -185,26 +204,21 @@ CYLON_CAPI int cylon_window(const char *id, const int32_t *partition_cols, int n
   });
 }
 
+CYLON_CAPI int cylon_window(const char *id, const int32_t *partition_cols, int npartition, const int32_t *order_cols,
+                            const int32_t *ascending, int norder, const int32_t *funcs, const int32_t *spec_cols,
+                            const int64_t *spec_args, const char *const *names, int nspecs, int distributed,
+                            const char *dest) {
+  return window_call(id, partition_cols, npartition, order_cols, ascending, norder, nspecs, distributed, dest, WIN_LEAD,
+                     funcs, spec_cols, spec_args, names);
+}
+
 CYLON_CAPI int cylon_window_frames(const char *id, const int32_t *partition_cols, int npartition,
                                    const int32_t *order_cols, const int32_t *ascending, int norder,
                                    const int32_t *funcs, const int32_t *spec_cols, const int64_t *spec_args,
                                    const int64_t *preceding, const int64_t *following, const int64_t *min_periods,
                                    const char *const *names, int nspecs, int distributed, const char *dest) {
-  return guard([&] {
-    std::vector<bool> dirs;
-    for (int i = 0; i < norder; ++i) dirs.push_back(ascending == nullptr || ascending[i] != 0);
-    std::vector<WindowSpec> specs;
-    for (int i = 0; i < nspecs; ++i) {
-      if (funcs[i] < WIN_ROW_NUMBER || funcs[i] > WIN_ROLLING_MAX)
-        return status(Status(Code::Invalid, "window function " + std::to_string(funcs[i])));
-      specs.push_back({static_cast<WindowFunc>(funcs[i]), spec_cols ? spec_cols[i] : -1, spec_args ? spec_args[i] : 0,
-                       names && names[i] ? names[i] : "", preceding ? preceding[i] : 0, following ? following[i] : 0,
-                       min_periods ? min_periods[i] : 1});
-    }
-    return status(WindowTable(id, std::vector<int32_t>(partition_cols, partition_cols + npartition),
-                              std::vector<int32_t>(order_cols, order_cols + norder), dirs, specs, dest,
-                              distributed != 0));
-  });
+  return window_call(id, partition_cols, npartition, order_cols, ascending, norder, nspecs, distributed, dest,
+                     WIN_ROLLING_MAX, funcs, spec_cols, spec_args, names, preceding, following, min_periods);
 }
 
 CYLON_CAPI int cylon_window_range_frames(const char *id, const int32_t *partition_cols, int npartition,
@@ -214,22 +228,9 @@ CYLON_CAPI int cylon_window_range_frames(const char *id, const int32_t *partitio
                                          const double *preceding_f, const double *following_f,
                                          const int32_t *offset_is_float, const int64_t *min_periods,
                                          const char *const *names, int nspecs, int distributed, const char *dest) {
-  return guard([&] {
-    std::vector<bool> dirs;
-    for (int i = 0; i < norder; ++i) dirs.push_back(ascending == nullptr || ascending[i] != 0);
-    std::vector<WindowSpec> specs;
-    for (int i = 0; i < nspecs; ++i) {
-      if (funcs[i] < WIN_ROW_NUMBER || funcs[i] > WIN_RANGE_MAX)
-        return status(Status(Code::Invalid, "window function " + std::to_string(funcs[i])));
-      specs.push_back({static_cast<WindowFunc>(funcs[i]), spec_cols ? spec_cols[i] : -1, spec_args ? spec_args[i] : 0,
-                       names && names[i] ? names[i] : "", preceding ? preceding[i] : 0, following ? following[i] : 0,
-                       min_periods ? min_periods[i] : 1, preceding_f ? preceding_f[i] : 0.0,
-                       following_f ? following_f[i] : 0.0, offset_is_float != nullptr && offset_is_float[i] != 0});
-    }
-    return status(WindowTable(id, std::vector<int32_t>(partition_cols, partition_cols + npartition),
-                              std::vector<int32_t>(order_cols, order_cols + norder), dirs, specs, dest,
-                              distributed != 0));
-  });
+  return window_call(id, partition_cols, npartition, order_cols, ascending, norder, nspecs, distributed, dest,
+                     WIN_RANGE_MAX, funcs, spec_cols, spec_args, names, preceding, following, min_periods, preceding_f,
+                     following_f, offset_is_float);
 }
 
 CYLON_CAPI int cylon_window_nav(const char *id, const int32_t *partition_cols, int npartition,
@@ -239,23 +240,9 @@ CYLON_CAPI int cylon_window_nav(const char *id, const int32_t *partition_cols, i
                                 const int32_t *offset_is_float, const int64_t *min_periods,
                                 const int32_t *ignore_nulls, const int64_t *limit, const char *const *names,
                                 int nspecs, int distributed, const char *dest) {
-  return guard([&] {
-    std::vector<bool> dirs;
-    for (int i = 0; i < norder; ++i) dirs.push_back(ascending == nullptr || ascending[i] != 0);
-    std::vector<WindowSpec> specs;
-    for (int i = 0; i < nspecs; ++i) {
-      if (funcs[i] < WIN_ROW_NUMBER || funcs[i] > WIN_CUME_DIST)
-        return status(Status(Code::Invalid, "window function " + std::to_string(funcs[i])));
-      specs.push_back({static_cast<WindowFunc>(funcs[i]), spec_cols ? spec_cols[i] : -1, spec_args ? spec_args[i] : 0,
-                       names && names[i] ? names[i] : "", preceding ? preceding[i] : 0, following ? following[i] : 0,
-                       min_periods ? min_periods[i] : 1, preceding_f ? preceding_f[i] : 0.0,
-                       following_f ? following_f[i] : 0.0, offset_is_float != nullptr && offset_is_float[i] != 0,
-                       ignore_nulls != nullptr && ignore_nulls[i] != 0, limit ? limit[i] : 0});
-    }
-    return status(WindowTable(id, std::vector<int32_t>(partition_cols, partition_cols + npartition),
-                              std::vector<int32_t>(order_cols, order_cols + norder), dirs, specs, dest,
-                              distributed != 0));
-  });
+  return window_call(id, partition_cols, npartition, order_cols, ascending, norder, nspecs, distributed, dest,
+                     WIN_CUME_DIST, funcs, spec_cols, spec_args, names, preceding, following, min_periods, preceding_f,
+                     following_f, offset_is_float, ignore_nulls, limit);
 }
 
 CYLON_CAPI int cylon_window_moment_frames(const char *id, const int32_t *partition_cols, int npartition,
@@ -266,23 +253,9 @@ CYLON_CAPI int cylon_window_moment_frames(const char *id, const int32_t *partiti
                                           const int32_t *offset_is_float, const int64_t *min_periods,
                                           const int32_t *ignore_nulls, const int64_t *limit, const int32_t *ddof,
                                           const char *const *names, int nspecs, int distributed, const char *dest) {
-  return guard([&] {
-    std::vector<bool> dirs;
-    for (int i = 0; i < norder; ++i) dirs.push_back(ascending == nullptr || ascending[i] != 0);
-    std::vector<WindowSpec> specs;
-    for (int i = 0; i < nspecs; ++i) {
-      if (funcs[i] < WIN_ROW_NUMBER || funcs[i] > WIN_RANGE_STD)
-        return status(Status(Code::Invalid, "window function " + std::to_string(funcs[i])));
-      specs.push_back({static_cast<WindowFunc>(funcs[i]), spec_cols ? spec_cols[i] : -1, spec_args ? spec_args[i] : 0,
-                       names && names[i] ? names[i] : "", preceding ? preceding[i] : 0, following ? following[i] : 0,
-                       min_periods ? min_periods[i] : 1, preceding_f ? preceding_f[i] : 0.0,
-                       following_f ? following_f[i] : 0.0, offset_is_float != nullptr && offset_is_float[i] != 0,
-                       ignore_nulls != nullptr && ignore_nulls[i] != 0, limit ? limit[i] : 0, ddof ? ddof[i] : 1});
-    }
-    return status(WindowTable(id, std::vector<int32_t>(partition_cols, partition_cols + npartition),
-                              std::vector<int32_t>(order_cols, order_cols + norder), dirs, specs, dest,
-                              distributed != 0));
-  });
+  return window_call(id, partition_cols, npartition, order_cols, ascending, norder, nspecs, distributed, dest,
+                     WIN_RANGE_STD, funcs, spec_cols, spec_args, names, preceding, following, min_periods, preceding_f,
+                     following_f, offset_is_float, ignore_nulls, limit, ddof);
 }
 
 CYLON_CAPI int cylon_asof_join(const char *left_id, const char *right_id, int left_on, int right_on,

@@ -369,40 +369,30 @@ class Table(PandasOpsMixin):
     def nsmallest(self, n: int, columns) -> "Table":
         return self.topk(n, columns, ascending=True)
 
-    # WindowFunc numbers (csrc/cylon/table.hpp)
-    _WINDOW_FUNCS = {"row_number": 0, "rank": 1, "dense_rank": 2, "cumcount": 3, "cumsum": 4, "cummin": 5,
-                     "cummax": 6, "lag": 7, "lead": 8}
-    # framed functions: they go through C.window_frames, which C.window's numbering stops short of
-    _ROLLING_FUNCS = {"rolling_count": 9, "rolling_sum": 10, "rolling_mean": 11, "rolling_min": 12,
-                      "rolling_max": 13}
-    # RANGE frames: they go through C.window_range_frames
-    _RANGE_FUNCS = {"range_count": 14, "range_sum": 15, "range_mean": 16, "range_min": 17, "range_max": 18}
-    # navigation and distribution functions: they go through C.window_nav
-    _NAV_FUNCS = {"first_value": 19, "last_value": 20, "nth_value": 21, "ffill": 22, "bfill": 23, "ntile": 24,
-                  "percent_rank": 25, "cume_dist": 26}
-    # VAR / STD over ROWS and RANGE frames: they go through C.window_moment_frames
-    _MOMENT_FUNCS = {"rolling_var": 27, "rolling_std": 28, "range_var": 29, "range_std": 30}
+    # function name -> (WindowFunc number of csrc/cylon/table.hpp, the family that says how its spec reads)
+    _WINDOW_FUNCS = {
+        "row_number": (0, "ranking"), "rank": (1, "ranking"), "dense_rank": (2, "ranking"),
+        "cumcount": (3, "running"), "cumsum": (4, "running"), "cummin": (5, "running"), "cummax": (6, "running"),
+        "lag": (7, "shift"), "lead": (8, "shift"),
+        "rolling_count": (9, "rolling"), "rolling_sum": (10, "rolling"), "rolling_mean": (11, "rolling"),
+        "rolling_min": (12, "rolling"), "rolling_max": (13, "rolling"),
+        "range_count": (14, "range"), "range_sum": (15, "range"), "range_mean": (16, "range"),
+        "range_min": (17, "range"), "range_max": (18, "range"),
+        "first_value": (19, "pick"), "last_value": (20, "pick"), "nth_value": (21, "nth"),
+        "ffill": (22, "fill"), "bfill": (23, "fill"),
+        "ntile": (24, "ntile"), "percent_rank": (25, "dist"), "cume_dist": (26, "dist"),
+        "rolling_var": (27, "moment"), "rolling_std": (28, "moment"), "range_var": (29, "moment"),
+        "range_std": (30, "moment")}
+    # The engine's entry points, narrowest first.  Each takes the functions up to its largest WindowFunc
+    # number and these fields of a _window_record, one list per field, in this order.
+    _WINDOW_BASE = ("fid", "col", "arg", "name")
+    _WINDOW_RANGE = _WINDOW_BASE + ("pre", "fol", "pre_f", "fol_f", "is_float", "minp")
+    _WINDOW_LEVELS = (("window", 8, _WINDOW_BASE),
+                      ("window_frames", 13, _WINDOW_BASE + ("pre", "fol", "minp")),
+                      ("window_range_frames", 18, _WINDOW_RANGE),
+                      ("window_nav", 26, _WINDOW_RANGE + ("ignore_nulls", "limit")),
+                      ("window_moment_frames", 30, _WINDOW_RANGE + ("ignore_nulls", "limit", "ddof")))
     _UNBOUNDED = (1 << 63) - 1
-
-    @classmethod
-    def _is_rolling(cls, spec):
-        return (not isinstance(spec, str) and len(spec) > 0 and isinstance(spec[0], str)
-                and spec[0].lower() in cls._ROLLING_FUNCS)
-
-    @classmethod
-    def _is_range(cls, spec):
-        return (not isinstance(spec, str) and len(spec) > 0 and isinstance(spec[0], str)
-                and spec[0].lower() in cls._RANGE_FUNCS)
-
-    @classmethod
-    def _is_nav(cls, spec):
-        fn = spec if isinstance(spec, str) else (spec[0] if len(spec) > 0 else None)
-        return isinstance(fn, str) and fn.lower() in cls._NAV_FUNCS
-
-    @classmethod
-    def _is_moment(cls, spec):
-        return (not isinstance(spec, str) and len(spec) > 0 and isinstance(spec[0], str)
-                and spec[0].lower() in cls._MOMENT_FUNCS)
 
     def _window_keys(self, partition_by, order_by, ascending):
         part = self._resolve_columns(partition_by) if partition_by is not None else []
@@ -412,161 +402,112 @@ class Table(PandasOpsMixin):
             raise ValueError(f"{len(asc)} ascending flags for {len(order)} order columns")
         return part, order, asc
 
-    def _window_spec(self, spec):
-        """(WindowFunc number, value column, LAG / LEAD offset) of a spec without a frame"""
-        spec = (spec,) if isinstance(spec, str) else tuple(spec)
+    def _window_record(self, spec, level=4):
+        """A spec as a dict of fid (WindowFunc number), col (value column, -1: none), arg (LAG / LEAD offset,
+        k of nth_value and ntile), pre, fol, pre_f, fol_f, is_float (the frame; in a range frame a float
+        offset makes both offsets floats -- an int beside it is converted -- and None stays the integer
+        that means unbounded), minp, ignore_nulls, limit and ddof, each at the engine's default where the
+        function does not read it.  A function above _WINDOW_LEVELS[level], or a framed one given as a bare
+        string, is unknown.  Values the engine refuses (k < 1, a negative limit or ddof, min_periods < 1,
+        ignore_nulls on nth_value) are left to it."""
+        bare = isinstance(spec, str)
+        spec = (spec,) if bare else tuple(spec)
         fn = str(spec[0]).lower() if spec else ""
-        if fn not in self._WINDOW_FUNCS:
+        fid, family = self._WINDOW_FUNCS.get(fn, (None, None))
+        if fid is None or fid > self._WINDOW_LEVELS[level][1] or (bare and family in ("rolling", "range", "moment")):
             raise ValueError(f"unknown window function {spec[0] if spec else spec!r}; "
-                             f"one of {sorted(self._WINDOW_FUNCS)}")
-        fid = self._WINDOW_FUNCS[fn]
-        if fid <= 2:
+                             f"one of {sorted(n for n, (i, _) in self._WINDOW_FUNCS.items() if i <= 8)}")
+        rec = dict(fid=fid, col=-1, arg=0, pre=0, fol=0, pre_f=0.0, fol_f=0.0, is_float=False, minp=1,
+                   ignore_nulls=False, limit=0, ddof=1)
+
+        def expect(lo, hi, form):
+            if len(spec) < lo or len(spec) > hi:
+                raise ValueError(f"window spec {spec!r}: expected {form}")
+
+        if family == "ranking" or family == "dist":
             if len(spec) != 1:
-                raise ValueError(f"window function {fn} takes no column")
-            return fid, -1, 0
-        if len(spec) < 2 or len(spec) > (3 if fid >= 7 else 2):
-            raise ValueError(f"window spec {spec!r}: expected ({fn!r}, column" + (", offset)" if fid >= 7 else ")"))
-        return fid, self._resolve_column(spec[1]), int(spec[2]) if len(spec) == 3 else (1 if fid >= 7 else 0)
+                raise ValueError(f"window function {fn} takes no " + ("column" if family == "ranking" else "argument"))
+        elif family == "ntile":
+            expect(2, 2, "('ntile', k)")
+            rec.update(arg=int(spec[1]))
+        elif family == "running":
+            expect(2, 2, f"({fn!r}, column)")
+            rec.update(col=self._resolve_column(spec[1]))
+        elif family == "shift":
+            expect(2, 3, f"({fn!r}, column, offset)")
+            rec.update(col=self._resolve_column(spec[1]), arg=int(spec[2]) if len(spec) == 3 else 1)
+        elif family == "rolling":
+            expect(4, 5, f"({fn!r}, column, preceding, following[, min_periods])")
+            pre, fol = (self._UNBOUNDED if b is None else int(b) for b in spec[2:4])
+            rec.update(pre=pre, fol=fol, col=self._resolve_column(spec[1]), minp=int(spec[4]) if len(spec) == 5 else 1)
+        elif family == "range":
+            expect(4, 5, f"({fn!r}, column, preceding, following[, min_periods])")
+            for b in spec[2:4]:
+                if b is not None and (isinstance(b, bool) or not isinstance(b, (int, float))):
+                    raise ValueError(f"window spec {spec!r}: an offset is an int, a float or None, not {b!r}")
+            is_float = any(isinstance(b, float) for b in spec[2:4])
+            pre, fol = (self._UNBOUNDED if b is None else (0 if is_float else int(b)) for b in spec[2:4])
+            pre_f, fol_f = (float(b) if is_float and b is not None else 0.0 for b in spec[2:4])
+            rec.update(pre=pre, fol=fol, pre_f=pre_f, fol_f=fol_f, is_float=is_float,
+                       col=self._resolve_column(spec[1]), minp=int(spec[4]) if len(spec) == 5 else 1)
+        elif family == "moment":  # the frame is read as rolling_mean resp. range_mean read theirs
+            expect(4, 6, f"({fn!r}, column, preceding, following[, min_periods[, ddof]])")
+            ddof = int(spec[5]) if len(spec) == 6 else 1
+            rec = self._window_record((fn.split("_")[0] + "_mean",) + spec[1:5])
+            rec.update(fid=fid, ddof=ddof)
+        elif family == "nth":
+            expect(3, 4, "('nth_value', column, k)")
+            rec.update(col=self._resolve_column(spec[1]), arg=int(spec[2]),
+                       ignore_nulls=bool(spec[3]) if len(spec) == 4 else False)
+        elif family == "pick":
+            expect(2, 3, f"({fn!r}, column[, ignore_nulls])")
+            rec.update(col=self._resolve_column(spec[1]), ignore_nulls=bool(spec[2]) if len(spec) == 3 else False)
+        else:  # fill
+            expect(2, 3, f"({fn!r}, column[, limit])")
+            limit = spec[2] if len(spec) == 3 else None
+            rec.update(col=self._resolve_column(spec[1]), limit=0 if limit is None else int(limit))
+        return rec
 
-    def _rolling_spec(self, spec):
-        """(WindowFunc number, value column, preceding, following, min_periods) of a rolling spec"""
-        spec = tuple(spec)
-        fn = spec[0].lower()
-        if len(spec) < 4 or len(spec) > 5:
-            raise ValueError(f"window spec {spec!r}: expected ({fn!r}, column, preceding, following[, min_periods])")
-        pre, fol = (self._UNBOUNDED if b is None else int(b) for b in spec[2:4])
-        return (self._ROLLING_FUNCS[fn], self._resolve_column(spec[1]), pre, fol,
-                int(spec[4]) if len(spec) == 5 else 1)
+    def _window_level(self, funcs):
+        """the narrowest entry point that takes every spec of the call (a spec that does not parse: the first)"""
+        fids = []
+        for spec in (funcs or {}).values():
+            fn = spec if isinstance(spec, str) else (spec[0] if len(spec) > 0 else None)
+            fid, family = self._WINDOW_FUNCS.get(fn.lower(), (0, "")) if isinstance(fn, str) else (0, "")
+            fids.append(0 if isinstance(spec, str) and family in ("rolling", "range", "moment") else fid)
+        return next(k for k, (_, top, _) in enumerate(self._WINDOW_LEVELS) if max(fids, default=0) <= top)
 
-    def _range_spec(self, spec):
-        """(WindowFunc number, value column, preceding, following, preceding_f, following_f, offset_is_float,
-        min_periods) of a range spec: a float offset makes the spec's offsets floats (an int beside it is
-        converted), None stays the integer that means unbounded"""
-        spec = tuple(spec)
-        fn = spec[0].lower()
-        if len(spec) < 4 or len(spec) > 5:
-            raise ValueError(f"window spec {spec!r}: expected ({fn!r}, column, preceding, following[, min_periods])")
-        for b in spec[2:4]:
-            if b is not None and (isinstance(b, bool) or not isinstance(b, (int, float))):
-                raise ValueError(f"window spec {spec!r}: an offset is an int, a float or None, not {b!r}")
-        is_float = any(isinstance(b, float) for b in spec[2:4])
-        ints = [self._UNBOUNDED if b is None else (0 if is_float else int(b)) for b in spec[2:4]]
-        floats = [float(b) if is_float and b is not None else 0.0 for b in spec[2:4]]
-        return (self._RANGE_FUNCS[fn], self._resolve_column(spec[1]), ints[0], ints[1], floats[0], floats[1], is_float,
-                int(spec[4]) if len(spec) == 5 else 1)
+    def _window_level_args(self, level, partition_by, order_by, ascending, funcs):
+        """(partition columns, order columns, ascending flags, one list per field of _WINDOW_LEVELS[level])"""
+        part, order, asc = self._window_keys(partition_by, order_by, ascending)
+        recs = [dict(self._window_record(spec, level), name="" if name is None else str(name))
+                for name, spec in (funcs or {}).items()]
+        return (part, order, asc, *([r[f] for r in recs] for f in self._WINDOW_LEVELS[level][2]))
 
-    def _nav_spec(self, spec):
-        """(WindowFunc number, value column, k, ignore_nulls, limit) of a navigation or distribution spec;
-        k < 1, a negative limit and ignore_nulls on nth_value are the engine's to refuse"""
-        spec = (spec,) if isinstance(spec, str) else tuple(spec)
-        fn = spec[0].lower()
-        fid = self._NAV_FUNCS[fn]
-        if fid >= 25:
-            if len(spec) != 1:
-                raise ValueError(f"window function {fn} takes no argument")
-            return fid, -1, 0, False, 0
-        if fid == 24:
-            if len(spec) != 2:
-                raise ValueError(f"window spec {spec!r}: expected ('ntile', k)")
-            return fid, -1, int(spec[1]), False, 0
-        if fid == 21:
-            if len(spec) < 3 or len(spec) > 4:
-                raise ValueError(f"window spec {spec!r}: expected ('nth_value', column, k)")
-            return fid, self._resolve_column(spec[1]), int(spec[2]), bool(spec[3]) if len(spec) == 4 else False, 0
-        if len(spec) < 2 or len(spec) > 3:
-            raise ValueError(f"window spec {spec!r}: expected ({fn!r}, column"
-                             + ("[, ignore_nulls])" if fid <= 20 else "[, limit])"))
-        opt = spec[2] if len(spec) == 3 else None
-        if fid <= 20:
-            return fid, self._resolve_column(spec[1]), 0, bool(opt), 0
-        return fid, self._resolve_column(spec[1]), 0, False, 0 if opt is None else int(opt)
+    def _window_args(self, partition_by, order_by, ascending, funcs):
+        return self._window_level_args(0, partition_by, order_by, ascending, funcs)
 
-    def _moment_spec(self, spec):
-        """(WindowFunc number, value column, preceding, following, preceding_f, following_f, offset_is_float,
-        min_periods, ddof) of a rolling_var / rolling_std / range_var / range_std spec; the frame is read as
-        rolling_mean resp. range_mean read theirs.  ddof < 0 and min_periods < 1 are the engine's to refuse"""
-        spec = tuple(spec)
-        fn = spec[0].lower()
-        if len(spec) < 4 or len(spec) > 6:
-            raise ValueError(f"window spec {spec!r}: expected ({fn!r}, column, preceding, following"
-                             f"[, min_periods[, ddof]])")
-        ddof = int(spec[5]) if len(spec) == 6 else 1
-        if fn.startswith("range_"):
-            _, col, p, f, pf, ff, isf, m = self._range_spec(("range_mean",) + spec[1:5])
-        else:
-            (_, col, p, f, m), (pf, ff, isf) = self._rolling_spec(("rolling_mean",) + spec[1:5]), (0.0, 0.0, False)
-        return self._MOMENT_FUNCS[fn], col, p, f, pf, ff, isf, m, ddof
+    def _window_frame_args(self, partition_by, order_by, ascending, funcs):
+        """_window_args plus the three frame lists, for a call with at least one rolling spec"""
+        return self._window_level_args(1, partition_by, order_by, ascending, funcs)
 
-    def _window_moment_args(self, partition_by, order_by, ascending, funcs):
-        """_window_nav_args plus ddof, for a call with at least one moment (framed VAR / STD) spec"""
-        plain = {n: ("row_number" if self._is_moment(s) else s) for n, s in (funcs or {}).items()}
-        part, order, asc, *lists = self._window_nav_args(partition_by, order_by, ascending, plain)
-        ddof = []
-        for i, spec in enumerate((funcs or {}).values()):
-            d = 1
-            if self._is_moment(spec):
-                # ids, cols, args, names, pre, fol, pre_f, fol_f, is_float, minp, ignore_nulls, limit
-                fid, col, p, f, pf, ff, isf, m, d = self._moment_spec(spec)
-                for k, v in ((0, fid), (1, col), (4, p), (5, f), (6, pf), (7, ff), (8, isf), (9, m)):
-                    lists[k][i] = v
-            ddof.append(d)
-        return (part, order, asc, *lists, ddof)
+    def _window_range_args(self, partition_by, order_by, ascending, funcs):
+        """_window_frame_args plus the float offsets, for a call with at least one range spec"""
+        return self._window_level_args(2, partition_by, order_by, ascending, funcs)
 
     def _window_nav_args(self, partition_by, order_by, ascending, funcs):
         """_window_range_args plus ignore_nulls and limit, for a call with at least one navigation or
         distribution spec"""
-        plain = {n: ("row_number" if self._is_nav(s) else s) for n, s in (funcs or {}).items()}
-        part, order, asc, *lists = self._window_range_args(partition_by, order_by, ascending, plain)
-        ignore, limit = [], []
-        for i, spec in enumerate((funcs or {}).values()):
-            fid, col, k, ign, lim = self._nav_spec(spec) if self._is_nav(spec) else (lists[0][i], lists[1][i],
-                                                                                     lists[2][i], False, 0)
-            lists[0][i], lists[1][i], lists[2][i] = fid, col, k
-            ignore.append(ign)
-            limit.append(lim)
-        return (part, order, asc, *lists, ignore, limit)
+        return self._window_level_args(3, partition_by, order_by, ascending, funcs)
 
-    def _window_range_args(self, partition_by, order_by, ascending, funcs):
-        """_window_frame_args plus the float offsets, for a call with at least one range spec"""
-        part, order, asc = self._window_keys(partition_by, order_by, ascending)
-        lists = [[] for _ in range(10)]  # ids, cols, args, names, pre, fol, pre_f, fol_f, is_float, minp
-        for name, spec in (funcs or {}).items():
-            if self._is_range(spec):
-                fid, col, p, f, pf, ff, isf, m = self._range_spec(spec)
-                arg = 0
-            elif self._is_rolling(spec):
-                (fid, col, p, f, m), (arg, pf, ff, isf) = self._rolling_spec(spec), (0, 0.0, 0.0, False)
-            else:
-                (fid, col, arg), (p, f, pf, ff, isf, m) = self._window_spec(spec), (0, 0, 0.0, 0.0, False, 1)
-            for lst, v in zip(lists, (fid, col, arg, "" if name is None else str(name), p, f, pf, ff, isf, m)):
-                lst.append(v)
-        return (part, order, asc, *lists)
+    def _window_moment_args(self, partition_by, order_by, ascending, funcs):
+        """_window_nav_args plus ddof, for a call with at least one moment (framed VAR / STD) spec"""
+        return self._window_level_args(4, partition_by, order_by, ascending, funcs)
 
-    def _window_args(self, partition_by, order_by, ascending, funcs):
-        part, order, asc = self._window_keys(partition_by, order_by, ascending)
-        ids, cols, args, names = [], [], [], []
-        for name, spec in (funcs or {}).items():
-            fid, col, arg = self._window_spec(spec)
-            ids.append(fid)
-            cols.append(col)
-            args.append(arg)
-            names.append("" if name is None else str(name))
-        return part, order, asc, ids, cols, args, names
-
-    def _window_frame_args(self, partition_by, order_by, ascending, funcs):
-        """_window_args plus the three frame lists, for a call with at least one rolling spec"""
-        part, order, asc = self._window_keys(partition_by, order_by, ascending)
-        ids, cols, args, names, pre, fol, minp = [], [], [], [], [], [], []
-        for name, spec in (funcs or {}).items():
-            if self._is_rolling(spec):
-                fid, col, p, f, m = self._rolling_spec(spec)
-                arg = 0
-            else:
-                (fid, col, arg), (p, f, m) = self._window_spec(spec), (0, 0, 1)
-            for lst, v in ((ids, fid), (cols, col), (args, arg), (names, "" if name is None else str(name)),
-                           (pre, p), (fol, f), (minp, m)):
-                lst.append(v)
-        return part, order, asc, ids, cols, args, names, pre, fol, minp
+    def _window_call(self, prefix, partition_by, order_by, ascending, funcs):
+        level = self._window_level(funcs)
+        entry = getattr(C, prefix + self._WINDOW_LEVELS[level][0])
+        return self._wrap(entry(self._t, *self._window_level_args(level, partition_by, order_by, ascending, funcs)))
 
     def window(self, partition_by=None, order_by=None, ascending: Union[bool, List[bool]] = True,
                funcs: dict = None) -> "Table":
@@ -615,37 +556,14 @@ class Table(PandasOpsMixin):
         m - ddof <= 0, NaN where the frame holds a NaN or an infinity, never negative.  Every moment spec
         of a column reads one pyramid of merged (count, mean, M2) states, so nothing cancels on data far
         from zero (docs/semantics.md "Framed aggregates")."""
-        if any(self._is_moment(s) for s in (funcs or {}).values()):
-            return self._wrap(C.window_moment_frames(
-                self._t, *self._window_moment_args(partition_by, order_by, ascending, funcs)))
-        if any(self._is_nav(s) for s in (funcs or {}).values()):
-            return self._wrap(C.window_nav(self._t, *self._window_nav_args(partition_by, order_by, ascending, funcs)))
-        if any(self._is_range(s) for s in (funcs or {}).values()):
-            return self._wrap(C.window_range_frames(self._t, *self._window_range_args(partition_by, order_by,
-                                                                                       ascending, funcs)))
-        if any(self._is_rolling(s) for s in (funcs or {}).values()):
-            return self._wrap(C.window_frames(self._t, *self._window_frame_args(partition_by, order_by, ascending,
-                                                                                 funcs)))
-        return self._wrap(C.window(self._t, *self._window_args(partition_by, order_by, ascending, funcs)))
+        return self._window_call("", partition_by, order_by, ascending, funcs)
 
     def distributed_window(self, partition_by=None, order_by=None, ascending: Union[bool, List[bool]] = True,
                            funcs: dict = None) -> "Table":
         """window() after a shuffle by the partition columns (at least one when the world is larger than
         1); the output row order is unspecified.  Rolling, range, navigation, distribution and moment specs
         as in window()."""
-        if any(self._is_moment(s) for s in (funcs or {}).values()):
-            return self._wrap(C.distributed_window_moment_frames(
-                self._t, *self._window_moment_args(partition_by, order_by, ascending, funcs)))
-        if any(self._is_nav(s) for s in (funcs or {}).values()):
-            return self._wrap(C.distributed_window_nav(
-                self._t, *self._window_nav_args(partition_by, order_by, ascending, funcs)))
-        if any(self._is_range(s) for s in (funcs or {}).values()):
-            return self._wrap(C.distributed_window_range_frames(
-                self._t, *self._window_range_args(partition_by, order_by, ascending, funcs)))
-        if any(self._is_rolling(s) for s in (funcs or {}).values()):
-            return self._wrap(C.distributed_window_frames(
-                self._t, *self._window_frame_args(partition_by, order_by, ascending, funcs)))
-        return self._wrap(C.distributed_window(self._t, *self._window_args(partition_by, order_by, ascending, funcs)))
+        return self._window_call("distributed_", partition_by, order_by, ascending, funcs)
 
     def _fill(self, fn, by, order_by, ascending, limit, columns):
         part = self._resolve_columns(by) if by is not None else []
