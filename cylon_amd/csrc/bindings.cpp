@@ -345,6 +345,34 @@ PYBIND11_MODULE(_C, m) {
   m.def("string_length", &ops::StringLength, py::arg("a"), py::arg("unit"), rel);
   m.def("string_tile_bytes", &ops::StringTileBytes, rel);
   m.attr("string_max_pattern_bytes") = (int)strmatch::kStrMaxPatternBytes;
+  // K15 string transforms (ops/string_transforms.cpp); side: 1 left, 2 right, 3 both
+  m.def("string_slice", &ops::StringSlice, py::arg("a"), py::arg("start") = 0, py::arg("stop") = py::none(), rel);
+  m.def(
+      "string_strip",
+      [](const Column &a, int side, const std::optional<py::bytes> &chars) {
+        std::optional<std::string> c;
+        if (chars) c = std::string(*chars);
+        py::gil_scoped_release nogil;
+        return ops::StringStrip(a, side, c);
+      },
+      py::arg("a"), py::arg("side") = 3, py::arg("chars") = py::none());
+  m.def("string_case", &ops::StringCase, py::arg("a"), py::arg("upper"), rel);
+  m.def(
+      "string_concat",
+      [](const Column &a, const Column &b, const py::bytes &sep) {
+        const std::string s = sep;
+        py::gil_scoped_release nogil;
+        return ops::StringConcat(a, b, s);
+      },
+      py::arg("a"), py::arg("b"), py::arg("sep") = py::bytes(""));
+  m.def(
+      "string_replace",
+      [](const Column &a, const py::bytes &pat, const py::bytes &repl, int64_t max_replacements) {
+        const std::string p = pat, r = repl;
+        py::gil_scoped_release nogil;
+        return ops::StringReplace(a, p, r, max_replacements);
+      },
+      py::arg("a"), py::arg("pat"), py::arg("repl"), py::arg("max_replacements") = -1);
   m.def("project", &ops::Project, rel);
   m.def("merge", &ops::Merge, rel);
   m.def("slice", &ops::Slice, rel);

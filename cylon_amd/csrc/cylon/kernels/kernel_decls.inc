@@ -46,6 +46,21 @@ void str_compare(const ColView &a, const ColView &b, int b_scalar, int op, int64
 void str_match(const ColView &a, int kind, const uint8_t *pat, int64_t plen, int utf8, int64_t n, uint8_t *out,
                void *stream);
 void str_length(const ColView &a, int unit, int64_t n, int64_t *out, void *stream);
+/* strxform.hip: K15 string transforms (docs/semantics.md "String transforms"): slice, strip, case,
+   concat and replace as two passes around exclusive_scan.  x says which (strxform_common.hpp); lit
+   (device memory) holds its literal bytes; b is read by SX_CONCAT only.  A row is live when a.valid
+   and b.valid (each may be null; a broadcast operand's must be) say so; a row that is not live has
+   length 0 and its bytes are never read.  strx_lengths: lens[i] = the output length of row i.
+   strx_write: row i's bytes at out + out_off[i]; flag (SX_CASE, may be null): set to 1 when a live
+   row holds a byte >= 0x80, else left alone.  strx_case_flat: upper / lower of a column without
+   validity in one flat pass over its total = offsets[n] - offsets[0] bytes; out_off = the rebased
+   offsets (n + 1), flag as above (not null). */
+void strx_lengths(const ColView &a, const ColView &b, const strxform::StrXform &x, const uint8_t *lit, int64_t n,
+                  int64_t *lens, void *stream);
+void strx_write(const ColView &a, const ColView &b, const strxform::StrXform &x, const uint8_t *lit, int64_t n,
+                const int64_t *out_off, uint8_t *out, uint32_t *flag, void *stream);
+void strx_case_flat(const ColView &a, int upper, int64_t n, int64_t total, int64_t *out_off, uint8_t *out,
+                    uint32_t *flag, void *stream);
 void select_var_lengths(const ColView &a, const ColView &b, int b_bcast, const uint8_t *cond, int64_t n,
                         int64_t *out_lens, void *stream);
 void select_var_bytes(const ColView &a, const ColView &b, int b_bcast, const uint8_t *cond, int64_t n,

@@ -22,6 +22,10 @@
 
 namespace cylon {
 
+namespace strxform {
+struct StrXform;  // strxform_common.hpp: the arguments of a string transform
+}
+
 // Read-only column view handed to kernels.
 struct ColView {
   const uint8_t *data = nullptr;     // fixed width values or var-width bytes

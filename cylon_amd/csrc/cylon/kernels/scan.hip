@@ -345,6 +345,7 @@ void preload_semi_join();
 void preload_sort();
 void preload_strcast();
 void preload_strmatch();
+void preload_strxform();
 void preload_topk();
 void preload_window();
 void preload_window_nav();
@@ -379,6 +380,7 @@ void preload_device_code() {
   preload_sort();
   preload_strcast();
   preload_strmatch();
+  preload_strxform();
   preload_topk();
   preload_window();
   preload_window_nav();

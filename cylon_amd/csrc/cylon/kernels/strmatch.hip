@@ -37,6 +37,7 @@
 // with Arrow's host kernels; it has no substring / LIKE operators.
 #include "device_common.hpp"
 #include "strmatch_common.hpp"
+#include "strstage.hpp"
 
 namespace cylon {
 namespace hip {
@@ -44,13 +45,8 @@ namespace hip {
 using namespace strmatch;
 
 constexpr int kTile = kStrTileBytes;
-constexpr int kRowWaves = kBlock / kWave;
 
 int64_t string_tile_bytes() { return kTile; }
-
-__device__ __forceinline__ bool row_live(const uint8_t *va, const uint8_t *vb, int64_t r) {
-  return (va == nullptr || va[r] != 0) && (vb == nullptr || vb[r] != 0);
-}
 
 // k_str_prefix modes beyond the StrMatchKind values it takes as they are
 constexpr int kPrefixCompare = 16;
@@ -92,45 +88,6 @@ k_str_byte_length(ColView a, int64_t n, int64_t *__restrict__ out) {
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride)
     out[i] = (a.valid == nullptr || a.valid[i] != 0) ? a.offsets[i + 1] - a.offsets[i] : 0;
-}
-
-// Copy the bytes of rows [r0, r1) of c (span <= kTile) to tile + shift, shift = the source's
-// address modulo 16; rows that are not live (va / vb) are skipped.  Ends with a barrier.
-__device__ __forceinline__ int stage_rows(const ColView &c, const uint8_t *va, const uint8_t *vb, int64_t r0,
-                                          int64_t r1, uint8_t *tile) {
-  const int64_t b0 = c.offsets[r0];
-  const int span = (int)(c.offsets[r1] - b0);
-  if (span == 0) {
-    __syncthreads();
-    return 0;
-  }
-  const uint8_t *src = c.data + b0;
-  const int shift = (int)(reinterpret_cast<uintptr_t>(src) & 15u);
-  const int tid = threadIdx.x;
-  int any_dead = 0;
-  if (va != nullptr || vb != nullptr) {
-    const int64_t r = r0 + tid;
-    any_dead = __syncthreads_or(r < r1 && !row_live(va, vb, r));
-  }
-  if (!any_dead) {
-    int head = (16 - shift) & 15;
-    if (head > span) head = span;
-    for (int k = tid; k < head; k += kBlock) tile[shift + k] = src[k];
-    const int nv = (span - head) >> 4;
-    const uint4 *s4 = reinterpret_cast<const uint4 *>(src + head);
-    uint4 *d4 = reinterpret_cast<uint4 *>(tile + shift + head);
-    for (int k = tid; k < nv; k += kBlock) d4[k] = s4[k];
-    for (int k = head + (nv << 4) + tid; k < span; k += kBlock) tile[shift + k] = src[k];
-  } else {
-    const int lane = tid & (kWave - 1);
-    for (int64_t r = r0 + tid / kWave; r < r1; r += kRowWaves) {
-      if (!row_live(va, vb, r)) continue;
-      const int s = (int)(c.offsets[r] - b0), e = (int)(c.offsets[r + 1] - b0);
-      for (int k = s + lane; k < e; k += kWave) tile[shift + k] = src[k];
-    }
-  }
-  __syncthreads();
-  return shift;
 }
 
 __device__ __forceinline__ int64_t wave_sum(int64_t v) {

@@ -209,6 +209,25 @@ Column StringCompare(const Column &a, const Column &b, int op);
 Column StringMatch(const Column &a, int kind, const std::string &pattern, char escape);
 Column StringLength(const Column &a, int unit);
 int64_t StringTileBytes();  // kernels' string_tile_bytes(): the staged path's largest 256-row span
+// K15 string transforms on the column's device (kernels/strxform.hip; docs/semantics.md "String
+// transforms").  a is a STRING or BINARY column; the result has a's type and name, is null exactly
+// where an input cell is null (a null row has length 0) and has a validity array iff an input has one.
+//   StringSlice: units[start:stop] of every cell as Python slices, step 1 (no stop: the end of the
+//     cell; a negative index counts from the end); a unit is a code point of a STRING column and a
+//     byte of a BINARY one.
+//   StringStrip: side a strxform::StrStripSide; chars the set of bytes to remove (none: ASCII
+//     whitespace).  A non-ASCII set on a STRING column is Invalid.
+//   StringCase: ASCII upper / lower, and whether a live row held a byte >= 0x80.
+//   StringConcat: a[i] + sep + b[i]; a and b have the same kind, and either may have one row
+//     (broadcast; a null one makes every row null).
+//   StringReplace: leftmost non-overlapping replacement of the literal pat (not empty), at most
+//     max_replacements times per cell (< 0: all).
+// A literal (sep, pat, repl) of more than kStrMaxPatternBytes bytes is Invalid.
+Column StringSlice(const Column &a, int64_t start, const std::optional<int64_t> &stop);
+Column StringStrip(const Column &a, int side, const std::optional<std::string> &chars);
+std::pair<Column, bool> StringCase(const Column &a, bool upper);
+Column StringConcat(const Column &a, const Column &b, const std::string &sep);
+Column StringReplace(const Column &a, const std::string &pat, const std::string &repl, int64_t max_replacements);
 TablePtr Project(const TablePtr &t, const std::vector<int> &cols);
 TablePtr Merge(const std::vector<TablePtr> &tables);  // vertical concat
 TablePtr Slice(const TablePtr &t, int64_t offset, int64_t length);

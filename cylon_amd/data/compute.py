@@ -5,12 +5,17 @@ numpy on the host.  Here fixed-width columns stay on the table's device and the
 operators run as device tensor expressions (ROCm kernels on MI355X), with the
 validity byte-mask propagated explicitly.  String / binary columns stay on the
 device too: where / fill_null (kernels/select.hip), the string <-> number casts
-(kernels/strcast.hip) and the string predicates (kernels/strmatch.hip) --
+(kernels/strcast.hip), the string predicates (kernels/strmatch.hip) --
 comparisons of a string column with a str / bytes scalar or with a string column
 of the same kind, str_starts_with / str_ends_with / str_contains / str_like and
-str_length.  What does not fit those kernels (operands of different kinds, a
-pattern over C.string_max_pattern_bytes, arithmetic on strings) is evaluated by
-Arrow compute on the host, as in the reference, with the same values.
+str_length -- and the string transforms (kernels/strxform.hip), which produce a
+string column from a string column: str_slice, str_strip / str_lstrip /
+str_rstrip, str_upper / str_lower, str_concat (also `t + "x"` and `a + b` of
+string columns) and str_replace.  What does not fit those kernels (operands of
+different kinds, a pattern or literal over C.string_max_pattern_bytes, a
+non-ASCII strip set, Unicode case mapping of non-ASCII text, other arithmetic
+on strings) is evaluated by Arrow compute on the host, as in the reference,
+with the same values.
 
 Engine selection keeps the reference's `compute_engine` config key: "arrow"
 forces the host Arrow path, anything else uses the device path.
@@ -94,6 +99,8 @@ def binary_op(table, other, op: Callable, engine: str = "device"):
         oc = other_cols[i] if other_cols is not None else None
         if engine != "arrow":
             res = _string_compare(c, oc, other, op, dev)
+            if res is None and op is operator.add:
+                res = _string_add(c, oc, other, dev)
             if res is not None:
                 out.append(res)
                 continue
@@ -301,10 +308,225 @@ def str_length(table, unit="chars", engine=None):
     return table._wrap(C.Table(table.native.context(), out))
 
 
+# ---------------------------------------------------------------- string transforms (kernels/strxform.hip)
+_STRIP_SIDE = {"left": 1, "right": 2, "both": 3}
+_ASCII_WHITESPACE = b" \t\n\v\f\r"
+
+
+def _is_string(col) -> bool:
+    return col.type.type == T.STRING
+
+
+def _literal(c, value) -> Any:
+    """A literal as Arrow takes it beside the column c: str for a STRING column, bytes for BINARY."""
+    return value.decode("utf-8") if _is_string(c) else value
+
+
+def _host_bytes_map(arr, fn):
+    """fn over the cells (bytes) of a host binary array: what Arrow has no binary kernel for."""
+    return pa.array([None if v is None else fn(v) for v in arr.to_pylist()], type=arr.type)
+
+
+def _map_text(table, what, device_fn, arrow_fn, use_arrow):
+    """One transform over every (string / binary) column of the table: device_fn(col) -> Column on
+    the column's device, or arrow_fn(col, arrow array) -> arrow array on the host."""
+    cols = _text_columns(table, what)
+    if use_arrow:
+        out = [_from_arrow(c.name, arrow_fn(c, _arrow_col(c)), table.device) for c in cols]
+    else:
+        out = [device_fn(c) for c in cols]
+    return table._wrap(C.Table(table.native.context(), out))
+
+
+def _slice_index(v, what):
+    if v is None:
+        return None
+    if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+        raise TypeError(f"str_slice: {what} must be an integer or None, not {type(v).__name__}")
+    return int(v)
+
+
+def str_slice(table, start=None, stop=None, engine=None):
+    """Every cell's units[start:stop] as Python slices it (step 1): code points of a string column
+    (Arrow's utf8_slice_codeunits), bytes of a binary one (binary_slice).  A negative index counts
+    from the end of the cell; both ends are clamped."""
+    b, e = _slice_index(start, "start") or 0, _slice_index(stop, "stop")
+
+    def arrow(c, arr):
+        fn = pc.utf8_slice_codeunits if _is_string(c) else pc.binary_slice
+        return fn(arr, start=b, stop=e)
+    return _map_text(table, "str_slice", lambda c: C.string_slice(c, b, e), arrow, _engine_of(table, engine) == "arrow")
+
+
+def _str_strip(table, side, chars, engine):
+    what = {"both": "str_strip", "left": "str_lstrip", "right": "str_rstrip"}[side]
+    cols = _text_columns(table, what)
+    cs = None if chars is None else _pattern_bytes(chars)
+    ascii_set = cs is None or all(b < 0x80 for b in cs)
+    suffix = {"both": "trim", "left": "ltrim", "right": "rtrim"}[side]
+
+    def arrow(c, arr):
+        if not _is_string(c):  # Arrow trims text only: a binary column's cells are stripped one by one
+            how = {"both": "strip", "left": "lstrip", "right": "rstrip"}[side]
+            return _host_bytes_map(arr, lambda v: getattr(v, how)(_ASCII_WHITESPACE if cs is None else cs))
+        if cs is None:
+            return getattr(pc, "ascii_" + suffix + "_whitespace")(arr)
+        return getattr(pc, "utf8_" + suffix)(arr, characters=cs.decode("utf-8"))
+    use_arrow = _engine_of(table, engine) == "arrow" or (not ascii_set and any(_is_string(c) for c in cols))
+    return _map_text(table, what, lambda c: C.string_strip(c, _STRIP_SIDE[side], cs), arrow, use_arrow)
+
+
+def str_strip(table, chars=None, engine=None):
+    """Remove the leading and trailing characters of the set `chars` from every cell; without
+    `chars`, ASCII whitespace (space, \\t \\n \\v \\f \\r: Arrow's ascii_trim_whitespace -- Unicode
+    whitespace stays, unlike pandas).  With `chars`: Arrow's utf8_trim / ascii_trim.  A set with a
+    non-ASCII character on a string column is stripped by Arrow's host kernel."""
+    return _str_strip(table, "both", chars, engine)
+
+
+def str_lstrip(table, chars=None, engine=None):
+    return _str_strip(table, "left", chars, engine)
+
+
+def str_rstrip(table, chars=None, engine=None):
+    return _str_strip(table, "right", chars, engine)
+
+
+def _str_case(table, upper, ascii_only, engine):
+    what = "str_upper" if upper else "str_lower"
+    cols = _text_columns(table, what)
+    arrow_engine = _engine_of(table, engine) == "arrow"
+    out = []
+    for c in cols:
+        unicode_map = not ascii_only and _is_string(c)
+        if arrow_engine:
+            if unicode_map:
+                fn = pc.utf8_upper if upper else pc.utf8_lower
+            elif _is_string(c):
+                fn = pc.ascii_upper if upper else pc.ascii_lower
+            else:  # bytes.upper / lower map ASCII letters only
+                def fn(arr):
+                    return _host_bytes_map(arr, bytes.upper if upper else bytes.lower)
+            out.append(_from_arrow(c.name, fn(_arrow_col(c)), table.device))
+            continue
+        res, non_ascii = C.string_case(c, upper)
+        if unicode_map and non_ascii:
+            # a non-ASCII byte in a live row: Unicode case mapping is Arrow's, on the host
+            res = _from_arrow(c.name, (pc.utf8_upper if upper else pc.utf8_lower)(_arrow_col(c)), table.device)
+        out.append(res)
+    return table._wrap(C.Table(table.native.context(), out))
+
+
+def str_upper(table, ascii_only=False, engine=None):
+    """Upper case.  The device maps ASCII letters (Arrow's ascii_upper) and reports whether any live
+    cell holds a non-ASCII byte; a string column that does, with ascii_only=False, is mapped by
+    Arrow's utf8_upper on the host instead, so the answer is Unicode-correct either way and
+    all-ASCII data never leaves the device.  A binary column always maps ASCII letters only."""
+    return _str_case(table, True, ascii_only, engine)
+
+
+def str_lower(table, ascii_only=False, engine=None):
+    """Lower case; see str_upper."""
+    return _str_case(table, False, ascii_only, engine)
+
+
+def _concat_operand(c, other, device):
+    """The other side of a concat with column c: a Column of c's kind, or None when it does not fit."""
+    if isinstance(other, C.Column):
+        return other if is_text(other) and other.type.type == c.type.type else None
+    if isinstance(other, (str, bytes, bytearray)) or other is None:
+        if isinstance(other, str) and not _is_string(c):
+            other = other.encode("utf-8")
+        return _var_scalar(c, bytes(other) if isinstance(other, bytearray) else other, device)
+    return None
+
+
+def _arrow_concat(c, a_arr, b_arr, sep):
+    # a column past 2 GiB comes to the host with 64-bit offsets: the three arguments share one type
+    large = any(pa.types.is_large_string(x.type) or pa.types.is_large_binary(x.type) for x in (a_arr, b_arr))
+    if _is_string(c):
+        typ = pa.large_string() if large else pa.string()
+    else:
+        typ = pa.large_binary() if large else pa.binary()
+    return pc.binary_join_element_wise(a_arr.cast(typ), b_arr.cast(typ), pa.scalar(_literal(c, sep), type=typ))
+
+
+def str_concat(table, other, sep="", engine=None):
+    """a[i] + sep + other[i] for every column of the table (Arrow's binary_join_element_wise: null
+    where either side is null).  other: a str / bytes scalar (None: a null, every row is null), or
+    a table of as many string columns of the same kind, each of the table's length or one row."""
+    from .table import Table
+    cols = _text_columns(table, "str_concat")
+    sp = _pattern_bytes(sep)
+    if isinstance(other, Table):
+        ocols = _text_columns(other, "str_concat")
+        if len(ocols) != len(cols):
+            raise ValueError("str_concat: tables must have the same number of columns")
+    else:
+        ocols = [other] * len(cols)
+    use_arrow = _engine_of(table, engine) == "arrow" or len(sp) > C.string_max_pattern_bytes
+    out = []
+    for c, o in zip(cols, ocols):
+        b = _concat_operand(c, o, c.data.device)
+        if b is None:
+            raise TypeError(f"str_concat: cannot concatenate column {c.name} ({c.type}) with {type(o).__name__}"
+                            if not isinstance(o, C.Column) else
+                            f"str_concat: column {o.name} ({o.type}) has not the type of {c.name} ({c.type})")
+        if use_arrow or b.data.device != c.data.device:
+            a_arr, b_arr = _arrow_col(c), _arrow_col(b)
+            if c.length == 1 and b.length != 1:
+                a_arr = a_arr[0]
+            elif b.length == 1 and c.length != 1:
+                b_arr = b_arr[0]
+            out.append(_from_arrow(c.name, _arrow_concat(c, a_arr, b_arr, sp), table.device))
+        else:
+            out.append(C.string_concat(c, b, sp))
+    return table._wrap(C.Table(table.native.context(), out))
+
+
+def _string_add(c, oc, other, device):
+    """`+` of a string / binary column with a str / bytes scalar or a column of the same kind
+    (kernels/strxform.hip concat); None when the operands do not fit."""
+    if not is_text(c):
+        return None
+    if oc is not None:
+        if not is_text(oc) or oc.type.type != c.type.type or oc.length != c.length or \
+                oc.data.device != c.data.device:
+            return None
+        b = oc
+    elif isinstance(other, (str, bytes)):
+        b = _concat_operand(c, other, device)
+        if b is None:
+            return None
+    else:
+        return None
+    return C.string_concat(c, b, b"")
+
+
+def str_replace(table, pat, repl, n=-1, engine=None):
+    """Replace the leftmost non-overlapping occurrences of the literal `pat` by `repl`, at most n per
+    cell (n < 0: all), byte-wise: Python's bytes.replace, Arrow's replace_substring.  No regular
+    expressions; an empty pattern is an error."""
+    p, r = _pattern_bytes(pat), _pattern_bytes(repl)
+    if isinstance(n, bool) or not isinstance(n, (int, np.integer)):
+        raise TypeError("str_replace: n must be an integer")
+    n = -1 if n < 0 else int(n)
+    if not p:
+        raise C.CylonError("string replace: the pattern is empty")
+    limit = C.string_max_pattern_bytes
+
+    def arrow(c, arr):
+        return pc.replace_substring(arr, pattern=_literal(c, p), replacement=_literal(c, r),
+                                    max_replacements=None if n < 0 else n)
+    use_arrow = _engine_of(table, engine) == "arrow" or len(p) > limit or len(r) > limit
+    return _map_text(table, "str_replace", lambda c: C.string_replace(c, p, r, n), arrow, use_arrow)
+
+
 class StringMethods:
     """The `.str` accessor of a Table / DataFrame whose columns are all string / binary: each method
-    returns a table of the same shape (BOOL or INT64 columns), so `t[t["name"].str.like("A%")]`
-    filters through __getitem__, where a null counts as false."""
+    returns a table of the same shape -- BOOL or INT64 columns from the predicates, so
+    `t[t["name"].str.like("A%")]` filters through __getitem__, where a null counts as false; string /
+    binary columns from the transforms (slice, strip, upper / lower, cat, replace)."""
 
     def __init__(self, table, wrap=None):
         self._table = table
@@ -332,6 +554,46 @@ class StringMethods:
 
     def len_bytes(self):
         return self._wrap(str_length(self._table, "bytes"))
+
+    def slice(self, start=None, stop=None):
+        """Code points [start:stop] of every cell (bytes of a binary column); step 1 only."""
+        return self._wrap(str_slice(self._table, start, stop))
+
+    def __getitem__(self, key):
+        if not isinstance(key, slice):
+            raise TypeError("str[...] takes a slice")
+        if key.step not in (None, 1):
+            raise NotImplementedError("str[...]: a slice step other than 1 is not supported")
+        return self.slice(key.start, key.stop)
+
+    def strip(self, chars=None):
+        """Strip ASCII whitespace (chars=None; Unicode whitespace stays, unlike pandas) or the
+        characters of `chars` from both ends."""
+        return self._wrap(str_strip(self._table, chars))
+
+    def lstrip(self, chars=None):
+        return self._wrap(str_lstrip(self._table, chars))
+
+    def rstrip(self, chars=None):
+        return self._wrap(str_rstrip(self._table, chars))
+
+    def upper(self):
+        return self._wrap(str_upper(self._table))
+
+    def lower(self):
+        return self._wrap(str_lower(self._table))
+
+    def cat(self, other, sep=""):
+        """cell + sep + other: other a str / bytes scalar or a table / frame of string columns."""
+        other = getattr(other, "_table", other)  # a DataFrame's table
+        return self._wrap(str_concat(self._table, other, sep))
+
+    def replace(self, pat, repl, n=-1, regex=False):
+        """Literal replacement.  pandas' default was regex=True for long; here the default is the
+        literal, and regex=True raises NotImplementedError."""
+        if regex:
+            raise NotImplementedError("str.replace(regex=True): regular expressions are not supported")
+        return self._wrap(str_replace(self._table, pat, repl, n))
 
 
 def fill_null(table, value):

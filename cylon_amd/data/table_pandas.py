@@ -306,6 +306,7 @@ class PandasOpsMixin:
         return a.equals(b)
 
 
-# t["name"].str.startswith(p) / .endswith / .contains / .like / .len / .len_bytes (compute.StringMethods);
+# t["name"].str.startswith(p) / .endswith / .contains / .like / .len / .len_bytes, and the transforms
+# .slice / [a:b] / .strip / .lstrip / .rstrip / .upper / .lower / .cat / .replace (compute.StringMethods);
 # attached here so that the name `str` inside the class body stays the builtin
 PandasOpsMixin.str = property(lambda self: compute.StringMethods(self), doc=compute.StringMethods.__doc__)

@@ -483,7 +483,7 @@ def _frame_str(self):
 
 # df["name"].str.*: the Table accessor with DataFrame results (attached here so that the name `str`
 # inside the class body stays the builtin)
-DataFrame.str = property(_frame_str, doc="String predicates of the columns (data/compute.py StringMethods).")
+DataFrame.str = property(_frame_str, doc="String predicates and transforms of the columns (data/compute.py StringMethods).")
 
 
 class _FrameIndexer:
